@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """Benchmark of the LightGCN propagation hot path on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line.  ``--full`` adds everything
+else the line used to carry: the configs[2] and training-step measurements, the rank-local partition,
+and the CPU baselines (``cpu_baseline``, ``other_configs``, ``rank_local``).  ``--dump-outputs DIR``
+writes a fixed, seeded sample of rows of the last timed step's embedding table as ``DIR/*.npy``.
 
 One *step* = one ``get_embedding``: LAYERS sparse hops over the whole graph with the layer sum
 fused (the work src/lightgcn.py:91-99 does per mini-batch and per serving request).
@@ -16,7 +21,7 @@ roofline = algorithmic bytes of one hop (B_min, SURVEY.md 8d: nnz*8 + (N+1)*4 + 
            by the mean duration of one hop's launches, measured with events on the launch stream
            inside the timed region, against 8 TB/s HBM3E.
 cpu_baseline = the reference-semantics CPU path (oracle/, a port of the reference's PyG route:
-           unsorted COO, per-layer gcn_norm, gather -> scale -> index_add_) timed on this host.
+           unsorted COO, per-layer gcn_norm, gather -> scale -> index_add_) timed on this host (--full).
 """
 import argparse
 import json
@@ -49,13 +54,17 @@ def parse():
     ap.add_argument("--layers", type=int, default=LAYERS)
     ap.add_argument("--dim", type=int, default=DIM)
     ap.add_argument("--config", choices=["cosmetics", "small"], default="cosmetics")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-deep", action="store_true", help="skip the configs[2] (D=90, K=5) measurement that rides "
-                    "along on the default single-GPU run")
-    ap.add_argument("--no-train", action="store_true", help="skip the training-step measurements (configs[4]'s step on one "
-                    "GPU at D=64/K=3 and D=90/K=5, and its one-step CPU baseline) of the default single-GPU run")
-    ap.add_argument("--no-rank-local", action="store_true", help="skip the rank-local measurement (one rank of an 8-way "
-                    "partition on this GPU, collectives stubbed)")
+    ap.add_argument("--full", action="store_true", help="also run every measurement beyond the headline: the CPU baselines, "
+                    "and on the default single-GPU run configs[2], the training steps and the rank-local partition")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write a fixed, seeded sample "
+                    "of rows of the last step's embedding table (and their node ids) as DIR/*.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-deep", action="store_true", help="with --full: skip the configs[2] (D=90, K=5) measurement that "
+                    "rides along on the default single-GPU run")
+    ap.add_argument("--no-train", action="store_true", help="with --full: skip the training-step measurements (configs[4]'s "
+                    "step on one GPU at D=64/K=3 and D=90/K=5, and its one-step CPU baseline) of the default single-GPU run")
+    ap.add_argument("--no-rank-local", action="store_true", help="with --full: skip the rank-local measurement (one rank of "
+                    "an 8-way partition on this GPU, collectives stubbed)")
     ap.add_argument("--cpu-threads", type=int, default=0, help="threads for the CPU baseline (0 = auto)")
     ap.add_argument("--rehearse-partition", action="store_true", help="ONE GPU: run the N > 1 code path (process group with "
                     "device_id, PartitionedPropagator, RecordedForward, barrier fences, MAX over ranks) as a partition of one rank "
@@ -65,7 +74,10 @@ def parse():
                     "graph with its collectives (partition.RecordedForward)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N > 1 (nccl = RCCL; gloo only "
                     "to rehearse the N > 1 path with several ranks on ONE GPU)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def cpu_model():
@@ -354,6 +366,29 @@ def workload_name(args, world: int) -> str:
     return "configs[2]" if (args.layers, args.dim) == (5, 90) else "configs[1]"
 
 
+DUMP_BYTES = 48 << 20      # the dumped sample's size limit (table rows + their ids)
+DUMP_SEED = 20260917
+
+
+def dump_rows(n: int, dim: int):
+    """Node ids of the dumped sample: every row if the table fits DUMP_BYTES, else a fixed, seeded, sorted sample."""
+    import numpy as np
+    count = min(n, DUMP_BYTES // (4 * dim + 8))
+    if count == n:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=count, replace=False))
+
+
+def dump_outputs(directory: str, table, rows) -> None:
+    """``embedding.npy``: rows ``rows`` of the [N, D] result of get_embedding (float32); ``embedding_rows.npy``: their
+    node ids (float64, exact)."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    sample = table.index_select(0, torch.from_numpy(rows).to(table.device)).float().cpu().numpy()
+    np.save(os.path.join(directory, "embedding.npy"), sample)
+    np.save(os.path.join(directory, "embedding_rows.npy"), rows.astype(np.float64))
+
+
 def kernel_source_hash() -> str:
     """sha256 over the files that decide which bytes a hop moves: the kernels and the work plans."""
     import hashlib
@@ -461,7 +496,8 @@ def main():
         torch.cuda.synchronize()
 
     def measure(dim, layers, steps, warmup):
-        """W untimed steps, then exactly K timed steps between two fences; per-hop events on the launch stream."""
+        """W untimed steps, then exactly K timed steps between two fences; per-hop events on the launch stream.
+        "out" is the last timed step's result."""
         alphas = tuple([1.0 / (layers + 1)] * (layers + 1))
         x0 = synth.xavier_table(n, dim, SEED, dev)
         step = make_step(x0, alphas)
@@ -470,8 +506,9 @@ def main():
         propagate.HOP_EVENT_LOG = []
         fence()
         t0 = time.perf_counter()
-        for _ in range(steps):
+        for _ in range(steps - 1):
             step()
+        out = step()            # only the last result is kept: the steps before it allocate exactly as before
         fence()
         elapsed = time.perf_counter() - t0
         hop_events, propagate.HOP_EVENT_LOG = propagate.HOP_EVENT_LOG, None
@@ -485,7 +522,8 @@ def main():
             hop_ms, hop_mean_s = [0.0] * (steps * layers), elapsed / (steps * layers)
         bmin = synth.algorithmic_bytes_per_layer(n, nnz, dim)
         achieved = bmin / hop_mean_s if hop_mean_s > 0 else 0.0
-        return {"elapsed": elapsed, "hop_mean_s": hop_mean_s, "launches": len(hop_ms), "bmin": bmin, "achieved": achieved}
+        return {"elapsed": elapsed, "hop_mean_s": hop_mean_s, "launches": len(hop_ms), "bmin": bmin, "achieved": achieved,
+                "out": out}
 
     def traffic_of(dim):
         """HBM-side bytes per hop from separate rocprofv3 PMC passes (profiles/collect.sh): quoted only while the kernel
@@ -507,16 +545,25 @@ def main():
                 "launches_timed": m["launches"]}
 
     main_m = measure(args.dim, args.layers, args.steps, args.warmup)
+    last = main_m.pop("out")
+    if args.dump_outputs:
+        if partitioned:
+            last = pp.gather_users(last.clone())           # collective: every rank's own user rows, on every rank
+        if rank == 0:
+            dump_outputs(args.dump_outputs, last, dump_rows(n, args.dim))
+    del last
+    # everything below the headline runs with --full only
+    default_run = args.full and not partitioned and args.config == "cosmetics" and (args.layers, args.dim) == (LAYERS, DIM)
     # configs[2] (same graph, 5 layers, emb_dim 90) rides along on the default single-GPU run: it is the configuration
     # furthest below its roofline, so the driver's own clock sees it too
     deep_m = None
-    if not partitioned and args.config == "cosmetics" and (args.layers, args.dim) == (LAYERS, DIM) and not args.no_deep:
+    if default_run and not args.no_deep:
         t0 = time.perf_counter()
         pg.prepare(90)
         deep_plan = time.perf_counter() - t0
         deep_steps = max(5, args.steps // 2)
         deep_m = measure(90, 5, deep_steps, args.warmup)
-    default_run = not partitioned and args.config == "cosmetics" and (args.layers, args.dim) == (LAYERS, DIM)
+        del deep_m["out"]
     train_lines, rank_local = [], None
     if default_run and not args.no_train:
         for t_dim, t_layers, t_steps, with_cpu in ((64, 3, max(20, args.steps), True), (90, 5, max(10, args.steps // 2), False)):
@@ -573,7 +620,7 @@ def main():
             line.setdefault("other_configs", []).extend(train_lines)
         if rank_local is not None:
             line["rank_local"] = rank_local
-        if not partitioned and not args.no_cpu_baseline:
+        if args.full and not partitioned and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(graph, args.layers, args.dim, args.cpu_threads)
         print(json.dumps(line), flush=True)
     if partitioned:

@@ -596,8 +596,9 @@ def partitioned_bpr_loss(pp: PartitionedPropagator, weight: Tensor, alphas: Sequ
         out = partitioned_embedding(pp, weight, alphas)
         mine = (users >= pp.u0) & (users < pp.u1)
         u, p, n = users[mine], pos[mine], neg[mine]
-        # a rank without own triples must still take part in the collectives of the backward pass
-        bpr_local = out[:1].sum() * 0.0
+        # a rank without own triples must still take part in the collectives of the backward pass; the row it reads is an
+        # item row (valid on every rank): row 0 may be another rank's user row, left undefined, and NaN * 0 is NaN
+        bpr_local = out[pp.n_users:pp.n_users + 1].sum() * 0.0
         if u.numel():
             scores = pair_scores(out, torch.stack((torch.cat([u, u]), torch.cat([p, n]))))
             m = u.numel()

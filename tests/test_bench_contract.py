@@ -35,7 +35,7 @@ def check_line(text, n_gpus, steps, warmup):
 
 def test_single_gpu_line(device):
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "small", "--steps", "3",
-                          "--warmup", "1"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+                          "--warmup", "1", "--full"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     d = check_line(out.stdout, 1, 3, 1)
     cb = d["cpu_baseline"]
@@ -80,3 +80,27 @@ def test_the_multi_gpu_code_path_rehearsed_with_one_rank_over_rccl(device):
     d = check_line(out.stdout, 1, 3, 1)
     assert "recorded as one HIP graph (collectives included)" in d["config"]["parallelism"], d["config"]["parallelism"]
     assert "cpu_baseline" not in d and d["roofline"]["launches_timed"] == 3 * 3
+
+
+def test_plain_line_is_lean_and_dumps_what_the_timed_path_computed(device, tmp_path):
+    """A plain run carries the headline only (the CPU baseline and the other measurements are behind --full), and
+    --dump-outputs writes the last timed step's embedding table: on the configs[0]-sized graph all of it, which must be
+    the oracle's get_embedding of the same seeded inputs."""
+    import numpy as np
+    import torch
+    from conftest import rel_fro
+    from gnn_ecommerce_amd import synth
+    from oracle import lightgcn_oracle as oracle
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "small", "--steps", "3", "--warmup", "1",
+                          "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    d = check_line(out.stdout, 1, 3, 1)
+    assert not {"cpu_baseline", "other_configs", "rank_local"} & set(d), sorted(d)
+    emb, rows = np.load(tmp_path / "embedding.npy"), np.load(tmp_path / "embedding_rows.npy")
+    g = synth.make_bipartite(**synth.CONFIG_SMALL, seed=0)
+    n = g.num_nodes
+    assert emb.dtype == np.float32 and emb.shape == (n, 64)
+    assert rows.dtype == np.float64 and np.array_equal(rows, np.arange(n))
+    ei, ew = g.coo()
+    want = oracle.get_embedding(synth.xavier_table(n, 64, 0), oracle.default_alpha(3), ei, ew, 3)
+    assert rel_fro(torch.from_numpy(emb), want) <= 1e-5
