@@ -76,7 +76,8 @@ class Comm:
     """The three places a rank talks to the others, as one object the callers go through: ``start`` an all-reduce of an
     item block (asynchronous; returns a handle), ``wait`` for it (the current stream waits, not the host), and
     ``reduce_now`` for small tensors that are read right away.  ``PartitionedTrainer`` substitutes a recording version
-    that cuts its HIP-graph capture at exactly these points (no collective is ever captured)."""
+    that cuts its HIP-graph capture at exactly these points (no collective is ever captured).  It also decides whether its
+    collectives may be captured into a graph (``capture_refusal``) and makes the ranks agree on a flag (``agree``)."""
 
     def __init__(self, world: int, group: Optional[dist.ProcessGroup]):
         self.world, self.group = world, group
@@ -97,6 +98,95 @@ class Comm:
     def reduce_now(self, t: Tensor) -> None:
         if self.active:
             dist.all_reduce(t, op=dist.ReduceOp.SUM, group=self.group)
+
+    def capture_refusal(self) -> Optional[str]:
+        """None if a HIP graph may capture these collectives, else why not.  Only a backend whose collectives are stream
+        operations can be captured: gloo moves CUDA tensors through the host from its own threads, and an attempt leaves
+        the launch stream in a broken capture.  (No process group at all: a measurement harness with the collectives
+        stubbed out -- nothing there to capture.)"""
+        if not self.active or not dist.is_initialized():
+            return None
+        backend = dist.get_backend(self.group)
+        return None if backend == "nccl" else f"backend {backend} cannot be captured"
+
+    def agree(self, flag: bool, device: torch.device) -> bool:
+        """``flag`` if it holds on EVERY rank (one MIN all-reduce of a tensor on ``device``), so that all ranks take the same
+        branch -- every rank replays a graph, or none does."""
+        if not self.active or not dist.is_initialized():
+            return bool(flag)
+        t = torch.tensor([int(flag)], dtype=torch.int32, device=device)
+        dist.all_reduce(t, op=dist.ReduceOp.MIN, group=self.group)
+        return bool(t.item())
+
+
+class GraphCapture:
+    """The one place the package captures HIP graphs.  ``with GraphCapture(device, pool) as cap:`` moves this thread to a
+    fresh side stream that first waits for the launch stream, and detaches ``propagate.HOP_EVENT_LOG`` (timing events cannot
+    be recorded into a graph); leaving the block ends a capture still open, restores the log and makes the launch stream
+    wait for the side stream.  Whatever goes wrong inside, the thread is then back on its own stream, which never was in
+    capture mode.  Inside, ``cap.begin()`` / ``cap.end()`` capture one graph each (``end`` returns it).
+
+    Capture mode "thread_local": the communication backend's own threads (gloo copies through the host; RCCL's watchdog
+    polls events) keep working while this thread captures -- legal, but under the default "global" mode any runtime call of
+    ANOTHER thread invalidates the capture."""
+
+    def __init__(self, device: torch.device, pool=None):
+        self.device, self.pool, self.graph = device, pool, None
+
+    def __enter__(self) -> "GraphCapture":
+        from . import propagate
+        self._launch = torch.cuda.current_stream(self.device)
+        self._side = torch.cuda.Stream(self.device)
+        self._side.wait_stream(self._launch)
+        self._log, propagate.HOP_EVENT_LOG = propagate.HOP_EVENT_LOG, None
+        self._on_side = torch.cuda.stream(self._side)
+        self._on_side.__enter__()
+        return self
+
+    def __exit__(self, *exc) -> None:
+        from . import propagate
+        try:
+            if self.graph is not None:
+                self.end()
+        finally:
+            self._on_side.__exit__(*exc)
+            propagate.HOP_EVENT_LOG = self._log
+            self._launch.wait_stream(self._side)
+
+    def begin(self) -> None:
+        graph = torch.cuda.CUDAGraph()
+        graph.capture_begin(pool=self.pool, capture_error_mode="thread_local")
+        self.graph = graph
+
+    def end(self) -> torch.cuda.CUDAGraph:
+        """Close the graph being captured.  Two collectives in a row leave an empty graph between them, and a capture that
+        failed at its first launch is empty: torch warns about those (replaying one is a no-op)."""
+        graph, self.graph = self.graph, None
+        with warnings.catch_warnings():
+            warnings.filterwarnings("ignore", message="The CUDA Graph is empty")
+            graph.capture_end()
+        return graph
+
+    @classmethod
+    def capture_one(cls, device: torch.device, fn):
+        """``fn()`` captured as one graph, after the device has finished all earlier work: ``(graph, fn's result, None)``, or
+        ``(None, None, "{type}: {message}")`` if anything failed -- the body first, else the capture itself.  Never raises an
+        ``Exception``."""
+        result, error = None, None
+        torch.cuda.synchronize(device)
+        try:
+            with cls(device) as cap:
+                cap.begin()
+                try:
+                    result = fn()
+                except Exception as exc:                      # noqa: BLE001 -- whatever the backend raises
+                    error = exc
+                graph = cap.end()
+        except Exception as exc:                              # noqa: BLE001 -- capture_begin, or an invalidated capture_end
+            error = error or exc
+        if error is not None:
+            return None, None, f"{type(error).__name__}: {error}"
+        return graph, result, None
 
 
 class HipOps(DeviceOps):
@@ -364,57 +454,15 @@ class RecordedForward:
 
     def __init__(self, pp: "PartitionedPropagator", x0: Tensor, alphas: Sequence[float], warmup: int = 2):
         self.pp, self.x0, self.alphas = pp, x0, tuple(float(a) for a in alphas)
-        self.graph, self.out, self.error = None, None, None
-        from . import propagate
+        self.graph, self.out = None, None
         for _ in range(max(warmup, 1)):                      # lazy plans, scratch tables, the communicator's first use
             pp.propagate_sum(x0, self.alphas)
-        ok = 1
-        active = getattr(pp.comm, "active", pp.world > 1)
-        # only a backend whose collectives are stream operations can be captured: gloo moves CUDA tensors through the host
-        # from its own threads, and an attempt leaves the launch stream in a broken capture
-        backend = dist.get_backend(pp.group) if dist.is_initialized() else None      # None: collectives stubbed out (a harness)
-        capturable = not active or backend in (None, "nccl")
-        if x0.is_cuda and RECORD_FORWARD and capturable:
-            torch.cuda.synchronize(x0.device)
-            log, propagate.HOP_EVENT_LOG = propagate.HOP_EVENT_LOG, None     # timing events cannot be recorded into a graph
-            # The capture runs on a side stream and is ended in a ``finally``: whatever goes wrong inside, this thread is
-            # back on its own stream, which never was in capture mode, before anything else is launched.
-            graph, out = torch.cuda.CUDAGraph(), None
-            current = torch.cuda.current_stream(x0.device)
-            side = torch.cuda.Stream(x0.device)
-            side.wait_stream(current)
-            try:
-                with torch.cuda.stream(side):
-                    # thread_local: the backend's watchdog thread keeps polling its events while this thread captures
-                    graph.capture_begin(capture_error_mode="thread_local")
-                    try:
-                        out = pp.propagate_sum(x0, self.alphas)
-                    except Exception as exc:                  # noqa: BLE001 -- whatever the backend raises: eager it is
-                        self.error, ok = f"{type(exc).__name__}: {exc}", 0
-                    finally:
-                        try:
-                            with warnings.catch_warnings():   # (a capture that failed at its first launch is empty)
-                                warnings.filterwarnings("ignore", message="The CUDA Graph is empty")
-                                graph.capture_end()
-                        except Exception as exc:              # noqa: BLE001 -- an invalidated capture ends with an error
-                            self.error, ok = self.error or f"{type(exc).__name__}: {exc}", 0
-            except Exception as exc:                          # noqa: BLE001 -- capture_begin itself
-                self.error, ok = self.error or f"{type(exc).__name__}: {exc}", 0
-            finally:
-                propagate.HOP_EVENT_LOG = log
-            current.wait_stream(side)
-            if ok:
-                self.graph, self.out = graph, out
-        else:
-            ok = 0
-            if not capturable:
-                self.error = f"backend {backend} cannot be captured"
-        if active and backend is not None:                    # every rank replays, or none does
-            flag = torch.tensor([ok], dtype=torch.int32, device=x0.device)
-            dist.all_reduce(flag, op=dist.ReduceOp.MIN, group=pp.group)
-            ok = int(flag.item())
-        if not ok:
-            self.graph, self.out = None, None
+        self.error = pp.comm.capture_refusal()
+        graph = out = None
+        if x0.is_cuda and self.error is None:
+            graph, out, self.error = GraphCapture.capture_one(x0.device, lambda: pp.propagate_sum(x0, self.alphas))
+        if pp.comm.agree(graph is not None, x0.device):
+            self.graph, self.out = graph, out
 
     @property
     def recorded(self) -> bool:
@@ -425,10 +473,6 @@ class RecordedForward:
             return self.pp.propagate_sum(self.x0, self.alphas)
         self.graph.replay()
         return self.out
-
-
-# "0": RecordedForward never records (the eager forward, as before)
-RECORD_FORWARD = os.environ.get("LGCN_RECORD_FORWARD", "1") == "1"
 
 
 class _ExchangeHandle:

@@ -19,28 +19,47 @@ import torch
 from torch import Tensor
 
 from . import _native
-from .partition import Comm, PartitionedPropagator, check_batch, step_backward, step_forward
+from .partition import Comm, GraphCapture, PartitionedPropagator, check_batch, step_backward, step_forward
 
 
 class _RecordingComm(Comm):
-    """``Comm`` that cuts the capture at every collective: end the graph being captured, note the collective, run it
-    eagerly, begin the next graph.  Handles are indices into ``self.handles`` so that a replay can wait for the work the
-    REPLAYED start returned."""
+    """``Comm`` that records a step as segments cut at every collective: end the graph being captured, note the
+    collective, run it eagerly, begin the next graph.  Handles are indices into ``self.handles`` so that a replay can wait
+    for the work the REPLAYED start returned.  ``actions``: ("graph", g) | ("start", tensor, slot) | ("wait", slot) |
+    ("reduce", tensor), in launch order."""
 
-    def __init__(self, inner: Comm, owner: "PartitionedTrainer"):
+    def __init__(self, inner: Comm, device: torch.device):
         super().__init__(inner.world, inner.group)
-        self.inner, self.owner = inner, owner
+        self.inner = inner
+        self.actions, self.handles = [], []
+        self.capture = GraphCapture(device, pool=torch.cuda.graph_pool_handle())
+
+    def record(self, body) -> None:
+        """``body()`` as segments; an exception inside it ends the open capture and leaves."""
+        with self.capture:
+            self.capture.begin()
+            body()
+            self.actions.append(("graph", self.capture.end()))
+
+    def _cut(self, run, action):
+        """Close the graph being captured, run the collective eagerly and note it, open the next graph."""
+        self.actions.append(("graph", self.capture.end()))
+        result = run()
+        self.actions.append(action)
+        self.capture.begin()
+        return result
 
     def start(self, block: Tensor):
-        slot = self.owner._cut(("start", block))
+        slot = len(self.handles)
+        self.handles.append(self._cut(lambda: self.inner.start(block), ("start", block, slot)))
         return ("slot", slot)
 
     def wait(self, handle) -> None:
         if handle is not None:
-            self.owner._cut(("wait", handle[1]))
+            self._cut(lambda: self.inner.wait(self.handles[handle[1]]), ("wait", handle[1]))
 
     def reduce_now(self, t: Tensor) -> None:
-        self.owner._cut(("reduce", t))
+        self._cut(lambda: self.inner.reduce_now(t), ("reduce", t))
 
 
 class PartitionedTrainer:
@@ -84,8 +103,7 @@ class PartitionedTrainer:
         self._full = None                          # the whole step as one graph (graphs="full"), once recorded
         self.full_error: Optional[str] = None
         self.warmup = int(warmup)
-        self._actions: Optional[list] = None       # recorded: ("graph", g) | ("start", tensor) | ("wait", slot) | ("reduce", t)
-        self._recording = None
+        self._actions: Optional[list] = None       # _RecordingComm.actions, once recorded
         self._steps_seen = 0
 
     # -- the step as straight-line code; collectives go through self.pp.comm -----------------------------------
@@ -125,111 +143,26 @@ class PartitionedTrainer:
             self._hyper_done[slot] = ev
 
     # -- recording ------------------------------------------------------------------------------------------------
-    def _cut(self, action):
-        """Called by _RecordingComm at a collective: close the graph being captured, note and RUN the collective, open the
-        next graph.  Returns the slot of a started exchange."""
-        rec = self._recording
-        self._end_capture(rec)
-        slot = None
-        if action[0] == "start":
-            slot = len(rec["handles"])
-            rec["handles"].append(rec["inner"].start(action[1]))
-            rec["actions"].append(("start", action[1], slot))
-        elif action[0] == "wait":
-            rec["inner"].wait(rec["handles"][action[1]])
-            rec["actions"].append(("wait", action[1]))
-        else:
-            rec["inner"].reduce_now(action[1])
-            rec["actions"].append(("reduce", action[1]))
-        rec["graph"] = torch.cuda.CUDAGraph()
-        rec["graph"].capture_begin(pool=rec["pool"], capture_error_mode="thread_local")
-        return slot
-
-    @staticmethod
-    def _end_capture(rec) -> None:
-        """Close the graph being captured and keep it.  Two collectives in a row leave an empty graph between them (torch
-        warns about those; replaying one is a no-op)."""
-        import warnings
-        with warnings.catch_warnings():
-            warnings.filterwarnings("ignore", message="The CUDA Graph is empty")
-            rec["graph"].capture_end()
-        rec["actions"].append(("graph", rec["graph"]))
-
     def _record(self) -> None:
-        # capture_error_mode "thread_local": the exchange started before a segment may still be running in the
-        # communication backend's own threads (gloo copies through the host; RCCL's watchdog polls events) while the next
-        # segment is being captured -- legal, but under the default "global" mode any runtime call of ANOTHER thread
-        # invalidates the capture.
-        from . import propagate
-        dev = self.w.device
         inner = self.pp.comm
-        rec = {"inner": inner, "actions": [], "handles": [], "pool": torch.cuda.graph_pool_handle(),
-               "graph": torch.cuda.CUDAGraph()}
-        self._recording = rec
-        stream = torch.cuda.Stream(dev)
-        stream.wait_stream(torch.cuda.current_stream(dev))
-        log, propagate.HOP_EVENT_LOG = propagate.HOP_EVENT_LOG, None
-        self.pp.comm = _RecordingComm(inner, self)
+        rec = self.pp.comm = _RecordingComm(inner, self.w.device)
         try:
-            with torch.cuda.stream(stream):
-                rec["graph"].capture_begin(pool=rec["pool"], capture_error_mode="thread_local")
-                try:
-                    self._body()
-                finally:
-                    self._end_capture(rec)
+            rec.record(self._body)
         finally:
             self.pp.comm = inner
-            propagate.HOP_EVENT_LOG = log
-            self._recording = None
-        torch.cuda.current_stream(dev).wait_stream(stream)
-        self._actions, self._n_slots = rec["actions"], len(rec["handles"])
+        self._actions, self._n_slots = rec.actions, len(rec.handles)
 
     def _record_full(self) -> bool:
         """The whole step, collectives included, as ONE graph.  Returns whether EVERY rank recorded it (else nothing is kept
-        and the caller records the segmented form).  The capture runs on a side stream and is always ended."""
-        import warnings
-        import torch.distributed as dist
-        from . import propagate
-        dev = self.w.device
+        and the caller records the segmented form)."""
         comm = self.pp.comm
-        active = getattr(comm, "active", self.pp.world > 1)
-        ok = 1
-        # (no process group at all: a measurement harness with the collectives stubbed out -- nothing there to capture)
-        backend = dist.get_backend(self.pp.group) if dist.is_initialized() else None
-        if active and backend not in (None, "nccl"):
-            self.full_error, ok = f"backend {backend} cannot be captured", 0
-        graph = torch.cuda.CUDAGraph()
-        if ok:
-            torch.cuda.synchronize(dev)
-            current, side = torch.cuda.current_stream(dev), torch.cuda.Stream(dev)
-            side.wait_stream(current)
-            log, propagate.HOP_EVENT_LOG = propagate.HOP_EVENT_LOG, None
-            try:
-                with torch.cuda.stream(side):
-                    graph.capture_begin(capture_error_mode="thread_local")
-                    try:
-                        self._body()
-                    except Exception as exc:                  # noqa: BLE001
-                        self.full_error, ok = f"{type(exc).__name__}: {exc}", 0
-                    finally:
-                        try:
-                            with warnings.catch_warnings():
-                                warnings.filterwarnings("ignore", message="The CUDA Graph is empty")
-                                graph.capture_end()
-                        except Exception as exc:              # noqa: BLE001
-                            self.full_error, ok = self.full_error or f"{type(exc).__name__}: {exc}", 0
-            except Exception as exc:                          # noqa: BLE001
-                self.full_error, ok = self.full_error or f"{type(exc).__name__}: {exc}", 0
-            finally:
-                propagate.HOP_EVENT_LOG = log
-            current.wait_stream(side)
-        if active and backend is not None:
-            flag = torch.tensor([ok], dtype=torch.int32, device=dev)
-            dist.all_reduce(flag, op=dist.ReduceOp.MIN, group=self.pp.group)
-            ok = int(flag.item())
-        if ok:
+        self.full_error = comm.capture_refusal()
+        graph = None
+        if self.full_error is None:
+            graph, _, self.full_error = GraphCapture.capture_one(self.w.device, self._body)
+        if comm.agree(graph is not None, self.w.device):
             self._full = graph
-        return bool(ok)
+        return self._full is not None
 
     def _replay(self) -> None:
         if self._full is not None:
