@@ -548,13 +548,8 @@ class Operator:
         0.4 M); a graph whose hubs are heavier keeps the full step.  One host sync, once per operator."""
         if self._row_stats is None:
             p = self.plan
-            deg = (self.rowptr[p.row_begin + 1:p.row_end + 1] - self.rowptr[p.row_begin:p.row_end]).double()
-            s1, s2 = torch.stack((deg.sum(), (deg * deg).sum())).tolist()
-            self._row_stats = (s1, s2, max(p.row_end - p.row_begin, 1))
-        s1, s2, rows = self._row_stats
-        if s1 <= 0:
-            return True
-        return n_ids / 4.0 * (s2 / s1 + s1 / rows) <= LISTED_ROWS_MAX_SHARE * s1
+            self._row_stats = row_stats(self.rowptr, p.row_begin, p.row_end)
+        return listed_rows_pay(self._row_stats, n_ids)
 
     def partials(self, dim: int) -> Optional[Tensor]:
         n_slots = self.plan.n_slots
@@ -633,7 +628,27 @@ class Operator:
 
 
 _rows_scratch: Dict[tuple, Tuple[Tensor, Tensor]] = {}
-LISTED_ROWS_MAX_SHARE = float(os.environ.get("LGCN_LISTED_ROWS_MAX_SHARE", "0.4"))   # Operator.listed_rows_pay
+LISTED_ROWS_MAX_SHARE = float(os.environ.get("LGCN_LISTED_ROWS_MAX_SHARE", "0.4"))   # listed_rows_pay
+
+
+def row_stats(rowptr: Tensor, row_begin: int, row_end: int) -> Tuple[float, float, int]:
+    """(sum d, sum d^2, rows) of the row lengths d of rows [row_begin, row_end) of a CSR: what ``listed_rows_pay`` reads.
+    One host sync."""
+    deg = (rowptr[row_begin + 1:row_end + 1] - rowptr[row_begin:row_end]).double()
+    s1, s2 = torch.stack((deg.sum(), (deg * deg).sum())).tolist()
+    return s1, s2, max(row_end - row_begin, 1)
+
+
+def listed_rows_pay(stats: Tuple[float, float, int], n_ids: int) -> bool:
+    """The listed-rows rule of ``Operator.listed_rows_pay`` on given row statistics (``row_stats``).  A partition decides
+    with the statistics of the WHOLE item half, not of a rank's slice, so that every rank -- and the single-GPU path on the
+    same graph -- takes the same branch, and the ranks all-reduce tensors of the same shape."""
+    s1, s2, rows = stats
+    if s1 <= 0:
+        return True
+    return n_ids / 4.0 * (s2 / s1 + s1 / rows) <= LISTED_ROWS_MAX_SHARE * s1
+
+
 ROWS_SPLIT_ROOM = 16384      # partial rows beyond one per list position: 256-entry chunks up to 4 M listed entries
 
 

@@ -31,6 +31,7 @@ import torch.distributed as dist
 from torch import Tensor
 
 from . import _native
+from . import graph as _graph
 from .graph import CHUNK_LEN, SHORT_MAX, Operator, PropGraph, build_row_plan
 from .propagate import DeviceOps
 
@@ -72,6 +73,13 @@ def check_bipartite(edge_index: Tensor, n_users: int, n_items: int) -> None:
         raise ValueError("partitioned propagation needs a bipartite user|item edge list (ids < n_users are users)")
 
 
+def _require_dense(t: Tensor) -> None:
+    """A tensor reduced in place must be contiguous: RCCL refuses anything else, and gloo sums the wrong bytes of a strided
+    CUDA view (a padded [n_items, D] block) without a word."""
+    if not t.is_contiguous():
+        raise ValueError(f"a collective needs a contiguous tensor, got shape {tuple(t.shape)} strides {t.stride()}")
+
+
 class Comm:
     """The three places a rank talks to the others, as one object the callers go through: ``start`` an all-reduce of an
     item block (asynchronous; returns a handle), ``wait`` for it (the current stream waits, not the host), and
@@ -89,6 +97,7 @@ class Comm:
     def start(self, block: Tensor):
         if not self.active:
             return None
+        _require_dense(block)
         return dist.all_reduce(block, op=dist.ReduceOp.SUM, group=self.group, async_op=True)
 
     def wait(self, handle) -> None:
@@ -97,6 +106,7 @@ class Comm:
 
     def reduce_now(self, t: Tensor) -> None:
         if self.active:
+            _require_dense(t)
             dist.all_reduce(t, op=dist.ReduceOp.SUM, group=self.group)
 
     def capture_refusal(self) -> Optional[str]:
@@ -238,6 +248,8 @@ class PartitionedPropagator:
         # go through the tiled kernels, longer ones through chunks; a dense enough slice (world 2) may sweep.
         self.item_op = self._restrict_items(local.forward_op)
         self.local_nnz = int(mine.sum().item()) * 2
+        # the item half of the GLOBAL graph, for the listed-rows choice (listed_rows_pay): the same on every rank
+        self._item_stats = _graph.row_stats(rowptr, n_users, n)
         self._keep = (full, local)
         self._coo = (edge_index, full.edge_values)
         self._transposed = None
@@ -250,6 +262,13 @@ class PartitionedPropagator:
             return self.ops.restrict(op, self.n_users, self.num_nodes, ITEM_SHORT_MAX, sweep_cols=(self.u0, self.u1))
         except TypeError:                                  # arithmetic test doubles without the sweep argument
             return self.ops.restrict(op, self.n_users, self.num_nodes, ITEM_SHORT_MAX)
+
+    def listed_rows_pay(self, n_ids: int) -> bool:
+        """Whether the last item step of a scoring forward runs for ``n_ids`` listed rows (graph.listed_rows_pay).  Decided
+        on the statistics of the whole item half, not of this rank's slice: the choice sets the shape of that layer's
+        all-reduce ([len, D] listed table or [n_items, D] item block), so every rank must make the same one -- and it is
+        the choice the single-GPU path makes on the same graph."""
+        return _graph.listed_rows_pay(self._item_stats, n_ids)
 
     # -- hops ----------------------------------------------------------------------------------
     # A hop has two local pieces and one exchange:
@@ -348,9 +367,8 @@ class PartitionedPropagator:
         mix = tables.pop()
         out = torch.zeros_like(x0) if zero_foreign_rows else torch.empty_like(x0)
         pending = [None] * (k + 1)                                   # all-reduce of x_l[items]
-        listed_items = final_item_rows is not None and final_rows is not None and propagate.SCORED_ITEM_ROWS_ONLY
-        if listed_items and hasattr(item_op, "listed_rows_pay"):            # (arithmetic test doubles have no such method)
-            listed_items = item_op.listed_rows_pay(2 * final_item_rows.numel())
+        listed_items = (final_item_rows is not None and final_rows is not None and propagate.SCORED_ITEM_ROWS_ONLY
+                        and self.listed_rows_pay(2 * final_item_rows.numel()))
         uniform = all(a == alphas[0] for a in alphas)
         marks = []
         for layer in range(1, k + 1):
@@ -626,8 +644,9 @@ def partitioned_bpr_loss(pp: PartitionedPropagator, weight: Tensor, alphas: Sequ
     check_batch(weight, users, pos, neg)
     size = users.numel()
     from . import propagate
+    # the same answer on every rank (the two paths exchange different tensors): no rank-local quantity decides it
     seeded = (SEEDED_STEP and propagate.SPARSE_BACKWARD and pair_scores is None and hasattr(pp.ops, "seed_pull")
-              and pp.u1 > pp.u0 and torch.is_grad_enabled() and weight.requires_grad
+              and all(hi > lo for lo, hi in pp.ranges) and torch.is_grad_enabled() and weight.requires_grad
               and len(alphas) - 1 <= _native.MAX_TERMS - 1
               and 2 * size * propagate.SEED_ROWS_FACTOR <= weight.size(0))
     if seeded:

@@ -653,7 +653,9 @@ def seeded_sum(user_t, item_t, user_fwd, split: int, rows: Tensor, vals: Tensor,
     out = None
     for layer in range(1, k + 1):
         with _HopSpan():
-            nxt = ops.scratch_table(g_tab)
+            # an exchanged item block is reduced in place by a collective, which takes one dense run of memory: with an
+            # exchange the tables keep the dense layout instead of scratch_table's padded rows (D=90: stride 96)
+            nxt = ops.scratch_table(g_tab) if exchange is None else torch.empty_like(g_tab)
             if layer == 1:
                 mark = _seed_mark_buffer(dev, n) if SEED_MARKS else None
                 try:

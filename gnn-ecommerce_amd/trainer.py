@@ -67,7 +67,8 @@ class PartitionedTrainer:
     ``users, pos, neg``: int64 ``[batch]`` device tensors): forward on the partition, BPR + regulariser of the triples this
     rank owns, seeded backward with the per-hop item-block exchange, Adam over ``pp.owned_row_ranges()``.  Returns a
     device tensor ``[bpr, reg, loss]`` (global values, summed over the ranks; no host sync).  ``weight`` is updated in
-    place; its rows other ranks own are never read or written.
+    place; its rows other ranks own are never read or written.  Every step bumps ``weight``'s version counter, as an
+    in-place optimizer step does, so that caches keyed on it (``LightGCN.recommendK``'s table) see the update.
 
     ``graphs=True``: the first call records the step (after ``warmup`` eager steps that build every lazy plan and
     scratch buffer), later calls replay it.  Same launches, same order, same bits as the eager step.  ``graphs="full"``:
@@ -81,6 +82,7 @@ class PartitionedTrainer:
         if weight.dtype != torch.float32 or weight.dim() != 2 or not weight.is_contiguous():
             raise TypeError("weight must be a contiguous 2-D fp32 table")
         self.pp, self.w = pp, weight.detach()
+        self._caller = weight                      # whose version counter a step bumps (the kernels write through self.w)
         self.alphas = tuple(float(a) for a in alphas)
         self.lr, self.decay, self.batch, self.betas, self.eps = float(lr), float(decay), int(batch), betas, float(eps)
         dev = self.w.device
@@ -201,6 +203,9 @@ class PartitionedTrainer:
                 if not (self.full_graph and self._record_full()):
                     self._record()                 # the recording run IS this step (captured work does not execute ...
                 self._replay()                     # ... so it is replayed once right away)
+        # lgc_adam_step_hp writes the table where autograd's version counter cannot see it: bump it as optim.Adam does
+        # (host bookkeeping only, after any capture has ended)
+        torch.autograd.graph.increment_version(self._caller)
         self._steps_seen += 1
         return self.stats
 

@@ -557,17 +557,47 @@ def test_full_scale_properties(device, cosmetics_graph, dim, layers):
     assert torch.equal(pg.deg.cpu(), deg)
 
 
+def popularity_triples(g, b, seed):
+    """(users, pos, neg) drawn the way upstream's batch loader draws them (src/utils_v2.py:168-181): distinct random users,
+    each with a random one of its own purchases as the positive -- so positives come in proportion to item popularity --
+    and a uniform negative.  Host arrays, seeded."""
+    rng = np.random.default_rng(seed)
+    order = np.argsort(g.user, kind="stable")
+    count = np.bincount(g.user, minlength=g.n_users)
+    start = np.cumsum(count) - count
+    users = rng.choice(np.flatnonzero(count), size=b, replace=False)
+    pos = g.item[order[start[users] + (rng.random(b) * count[users]).astype(np.int64)]]
+    neg = rng.integers(0, g.n_items, size=b)
+    return (torch.from_numpy(users.astype(np.int64)), torch.from_numpy(pos.astype(np.int64) + g.n_users),
+            torch.from_numpy(neg.astype(np.int64) + g.n_users))
+
+
 def test_full_scale_training_step_against_the_oracle(device, cosmetics_graph):
     """BASELINE.json configs[4]'s step on one GPU (src/train_lightgcn.py:137-147: B = 1024, D = 64, K = 3 on the
     20.3 M-edge graph), seeded backward on: scores, bpr, reg and embedding.weight.grad against the oracle's
     train_step_loss + autograd on the host -- whole tensor, the <= 3B seed rows, 20 hub rows."""
-    g = cosmetics_graph
+    _full_scale_training_step(device, cosmetics_graph, 64, 3, "uniform")
+
+
+@pytest.mark.parametrize("dim,layers,draw", [pytest.param(90, 5, "uniform", id="d90_k5_uniform"),
+                                             pytest.param(64, 3, "popularity", id="d64_k3_popularity")])
+def test_full_scale_training_step_at_the_reference_shape_and_draw(device, cosmetics_graph, dim, layers, draw):
+    """The same step and gates at the reference's D = 90, K = 5, and with positives drawn like upstream's loader
+    (``popularity``): the regime where the listed last item step reads millions of entries and repeats hub rows (uniform
+    ids list ~0.4 M)."""
+    _full_scale_training_step(device, cosmetics_graph, dim, layers, draw)
+
+
+def _full_scale_training_step(device, g, dim, layers, draw):
     ei, ew = g.coo()
-    n, dim, layers, b, decay = g.num_nodes, 64, 3, 1024, 1e-4
-    gen = torch.Generator().manual_seed(11)
-    users = torch.randint(0, g.n_users, (b,), generator=gen)
-    pos = torch.randint(0, g.n_items, (b,), generator=gen) + g.n_users
-    neg = torch.randint(0, g.n_items, (b,), generator=gen) + g.n_users
+    n, b, decay = g.num_nodes, 1024, 1e-4
+    if draw == "uniform":
+        gen = torch.Generator().manual_seed(11)
+        users = torch.randint(0, g.n_users, (b,), generator=gen)
+        pos = torch.randint(0, g.n_items, (b,), generator=gen) + g.n_users
+        neg = torch.randint(0, g.n_items, (b,), generator=gen) + g.n_users
+    else:
+        users, pos, neg = popularity_triples(g, b, 11)
     w0 = synth.xavier_table(n, dim, 0)
     alpha = oracle.default_alpha(layers)
     torch.set_num_threads(min(32, torch.get_num_threads()))
@@ -579,8 +609,16 @@ def test_full_scale_training_step_against_the_oracle(device, cosmetics_graph):
     model.to(device)
     ud, pd_, nd = users.to(device), pos.to(device), neg.to(device)
     labels = oracle.batch_pos_neg_edges(ud, pd_, nd)
-    out = model(ei.to(device), labels, ew.to(device))
+    ei_d, ew_d = ei.to(device), ew.to(device)
+    out = model(ei_d, labels, ew_d)
     assert "ScoresFromTable" in type(out.grad_fn).__name__                        # the seeded path
+    # the regime the case claims: the last item step ran for the listed rows (4B ids) ...
+    item_deg = torch.bincount(ei[1], minlength=n)
+    listed_entries = int(item_deg[pos].sum() + item_deg[neg].sum())
+    assert lg.get_graph(ei_d, ew_d, n).halves()[1].listed_rows_pay(4 * b)
+    if draw == "popularity":                                                        # ... over millions of entries, hubs repeated
+        assert listed_entries >= 2_000_000 and torch.unique(pos).numel() < b, (listed_entries, torch.unique(pos).numel())
+    print(f"D={dim} K={layers} {draw}: listed item rows hold {listed_entries / 1e6:.2f} M entries")
     bpr = model.recommendation_loss(out[:b], out[b:], 0) * b
     reg = model.regularization_loss(ud, pd_, nd, decay)
     (bpr + reg).backward()
@@ -788,6 +826,62 @@ def test_band_sweep_matches_the_oracle_and_the_chunked_path(device, dim, monkeyp
     y66 = torch.empty_like(x66)
     sw.apply(x66, y66)
     assert rel_fro(y66[nu:].cpu(), oracle.lgconv(x66.cpu(), ei, ew)[nu:]) <= TOL
+
+
+@pytest.fixture(scope="module")
+def rank_slice():
+    """The item half of a small user|item graph as a rank of a partition holds it: only the edges whose user lies in
+    [c0, c1), 0 < c0 < c1 < n_users, with the GLOBAL per-edge values (the oracle's normalisation of the whole graph, fp32).
+    Returns (graph, c0, c1, slice edge_index, slice values) on the host."""
+    g, ei, ew = small_graph(8, 6000, 150, 90000)
+    val = oracle.gcn_norm(ei, ew, g.num_nodes)
+    c0, c1 = 1717, 4545
+    keep = (ei[1] >= g.n_users) & (ei[0] >= c0) & (ei[0] < c1)
+    return g, c0, c1, ei[:, keep].contiguous(), val[keep].contiguous()
+
+
+@pytest.mark.parametrize("bands", [1, 2, 4, 8])
+@pytest.mark.parametrize("dim", [61, 64, 68, 90, 96, 97, 128])
+def test_band_sweep_on_a_column_sub_range(device, rank_slice, dim, bands, monkeypatch):
+    """lgc_spmm_sweep on the item rows of a rank's slice: every column lies in [c0, c1) with c0 > 0 (a plan's bands are
+    cut inside that range, the kernels index the table from col_lo), at 1 / 2 / 4 / 8 bands and both step widths -- 4
+    entries per step (61..64 columns, and 97..128 in two passes) and 2 (68..96) -- against an fp64 evaluation of the same
+    slice on the host: norm-wise and worst row, rows outside the plan untouched, deterministic, the a / r / b epilogue and
+    a strided input table."""
+    from gnn_ecommerce_amd import graph as G
+    from gnn_ecommerce_amd.graph import Operator
+    g, c0, c1, sei, sval = rank_slice
+    n, nu = g.num_nodes, g.n_users
+    monkeypatch.setattr(G, "USE_SWEEP", "1")
+    pg = PropGraph(sei.to(device), sval.to(device), n, normalize=False)
+    op = pg.forward_op
+    sw = Operator.build(n, op.rowptr, op.entries, nu, n, 32, 256, sweep_cols=(c0, c1))
+    assert sw.sweep_cols == (c0, c1)
+    sw.sweep_bands = bands
+    groups = 2 if 64 < dim <= 96 else 4
+    x, r = synth.xavier_table(n, dim, 5), synth.xavier_table(n, dim, 6)
+    want = torch.zeros((n, dim), dtype=torch.float64).index_add_(0, sei[1], sval.double().view(-1, 1) * x.double()[sei[0]])[nu:]
+    xd, rd = x.to(device), r.to(device)
+    y = torch.full((n, dim), float("nan"), device=device)
+    sw.apply(xd, y)
+    dims = {k: (p.dims["groups"], p.dims["n_bands"], p.dims["n_entries"]) for k, p in sw._sweep.items()}
+    assert dims == {groups: (groups, bands, sei.size(1))}, dims
+    got = y[nu:].cpu()
+    assert rel_fro(got, want) <= TOL and worst_row_rel(got, want) <= TOL
+    assert torch.isnan(y[:nu]).all()                                   # only the rows of the plan are written
+    y2 = torch.full_like(y, float("nan"))
+    sw.apply(xd, y2)
+    assert torch.equal(y2[nu:], y[nu:])                                # deterministic
+    ye = torch.full_like(y, float("nan"))
+    sw.apply(xd, ye, a=0.5, r=rd, b=0.25)
+    want_e = 0.5 * want + 0.25 * r[nu:].double()
+    assert rel_fro(ye[nu:].cpu(), want_e) <= TOL and worst_row_rel(ye[nu:].cpu(), want_e) <= TOL
+    assert torch.isnan(ye[:nu]).all()
+    wide = torch.zeros((n, dim + 8), device=device)
+    wide[:, :dim] = xd
+    ys = torch.full_like(y, float("nan"))
+    sw.apply(wide[:, :dim], ys)
+    assert list(sw._sweep) == [groups] and torch.equal(ys[nu:], y[nu:])
 
 
 @pytest.mark.parametrize("rows,cols,k", [(1, 54571, 20), (7, 1000, 5), (3, 300, 256), (5, 64, 64), (2, 5000, 1),

@@ -81,7 +81,7 @@ def test_partitioned_propagate_matches_single_process_oracle(world, layers, dim,
         assert r["items_identical"]
 
 
-def _train_worker(rank, world, port, seeded, q):
+def _train_worker(rank, world, port, seeded, q, share=None):
     sys.path.insert(0, ROOT)
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     torch.set_num_threads(2)
@@ -89,8 +89,10 @@ def _train_worker(rank, world, port, seeded, q):
     try:
         from cpu_ops import CpuOps
         from oracle import lightgcn_oracle as oracle
-        from gnn_ecommerce_amd import synth
+        from gnn_ecommerce_amd import graph as G, synth
         from gnn_ecommerce_amd.partition import PartitionedPropagator, partitioned_bpr_loss
+        if share is not None:
+            G.LISTED_ROWS_MAX_SHARE = share
         g = synth.make_bipartite(400, 70, 3000, seed=11)
         ei, ew = g.coo()
         n, dim, layers, decay, batch = g.num_nodes, 32, 3, 1e-4, 64
@@ -149,26 +151,47 @@ def _train_worker(rank, world, port, seeded, q):
                       "grad_own_users": rel(w.grad[lo:hi], wr.grad[lo:hi]) if hi > lo else 0.0,
                       "grad_items": rel(w.grad[g.n_users:], wr.grad[g.n_users:]),
                       "grad_foreign_zero": bool((w.grad[:g.n_users][foreign] == 0).all()),
-                      "own_triples": int(((users >= lo) & (users < hi)).sum())}))
+                      "own_triples": int(((users >= lo) & (users < hi)).sum()),
+                      "listed": pp.listed_rows_pay(4 * batch)}))
     finally:
         dist.destroy_process_group()
 
 
-@pytest.mark.parametrize("seeded", [True, False], ids=["seeded_node", "dense_backward"])
-@pytest.mark.parametrize("world", [2, 3])
-def test_partitioned_training_step_matches_single_process_gradients(world, seeded):
-    """Row (e) of the hot-path contract end to end: forward, pair routing to the user's owner, BPR + regulariser,
-    backward on A^T with the item-gradient all-reduce -- against the oracle's autograd on one process."""
+def _run_train(world, seeded, share=None):
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     port = _free_port()
-    procs = [ctx.Process(target=_train_worker, args=(r, world, port, seeded, q)) for r in range(world)]
+    procs = [ctx.Process(target=_train_worker, args=(r, world, port, seeded, q, share)) for r in range(world)]
     for p in procs:
         p.start()
     results = dict(q.get(timeout=180) for _ in range(world))
     for p in procs:
         p.join(timeout=60)
         assert p.exitcode == 0
+    return results
+
+
+@pytest.mark.parametrize("seeded", [True, False], ids=["seeded_node", "dense_backward"])
+@pytest.mark.parametrize("world", [2, 3])
+def test_partitioned_training_step_matches_single_process_gradients(world, seeded):
+    """Row (e) of the hot-path contract end to end: forward, pair routing to the user's owner, BPR + regulariser,
+    backward on A^T with the item-gradient all-reduce -- against the oracle's autograd on one process.  At the default
+    listed-rows threshold a graph this small keeps the full last item step (the [n_items, D] exchange)."""
+    results = _run_train(world, seeded)
+    _check_train(world, results)
+    assert not any(r["listed"] for r in results.values())
+
+
+@pytest.mark.parametrize("world", [2, 3])
+def test_partitioned_training_step_through_the_listed_rows_exchange(world):
+    """The same step with the listed-rows threshold forced open: the seeded forward's last item step runs for the batch's
+    item rows only and its exchange is the [2B, D] table of those rows."""
+    results = _run_train(world, True, share=1e9)
+    _check_train(world, results)
+    assert all(r["listed"] for r in results.values())
+
+
+def _check_train(world, results):
     if world == 3:
         assert results[2]["own_triples"] == 0           # the collective path without any own pair
     for rank, r in results.items():
@@ -177,3 +200,59 @@ def test_partitioned_training_step_matches_single_process_gradients(world, seede
         assert r["grad_foreign_zero"], (rank, r)
         # two trainer steps: the update of the rows a rank owns equals torch.optim.Adam's on the single-process loss
         assert r["trainer_stats"] <= 1e-5 and r["trainer_rows"] <= 1e-4 and r["trainer_foreign"], (rank, r)
+
+
+def _decision_worker(rank, world, port, q):
+    sys.path.insert(0, ROOT)
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    torch.set_num_threads(2)
+    dist.init_process_group("gloo", init_method=f"file://{port}", rank=rank, world_size=world)
+    try:
+        from cpu_ops import CpuOps
+        from gnn_ecommerce_amd import graph as G, synth
+        from gnn_ecommerce_amd.graph import Operator
+        from gnn_ecommerce_amd.partition import PartitionedPropagator
+        g = synth.make_bipartite(400, 70, 3000, seed=11)
+        ei, ew = g.coo()
+        n, nu = g.num_nodes, g.n_users
+        pp = PartitionedPropagator(ei, ew, nu, g.n_items, rank, world, ops=CpuOps())
+        sweep = list(range(1, 4001))
+        new = torch.tensor([pp.listed_rows_pay(k) for k in sweep], dtype=torch.uint8)
+        # the rule on this rank's OWN slice of the item half (what the ranks used to decide with)
+        p = pp.item_op
+        local = G.row_stats(p.rowptr, p.row_begin, p.row_end)
+        old = torch.tensor([G.listed_rows_pay(local, k) for k in sweep], dtype=torch.uint8)
+        # the single-process choice: the item half of the whole graph's operator
+        rowptr = torch.cat([torch.zeros(1, dtype=torch.int32), torch.bincount(ei[1], minlength=n).cumsum(0).to(torch.int32)])
+        single_op = Operator.build(n, rowptr, torch.zeros((ei.size(1), 2), dtype=torch.int32), nu, n)
+        single = torch.tensor([single_op.listed_rows_pay(k) for k in sweep], dtype=torch.uint8)
+        got_new, got_old = [torch.empty_like(new) for _ in range(world)], [torch.empty_like(old) for _ in range(world)]
+        dist.all_gather(got_new, new)
+        dist.all_gather(got_old, old)
+        q.put((rank, {"new_equal": all(torch.equal(t, got_new[0]) for t in got_new),
+                      "new_is_single": bool(torch.equal(new, single)),
+                      "old_split": int(sum(int((t != got_old[0]).sum()) for t in got_old)),
+                      "both": (bool(new.any()), bool((new == 0).any()))}))
+    finally:
+        dist.destroy_process_group()
+
+
+def test_every_rank_makes_the_same_listed_rows_choice():
+    """partition.PartitionedPropagator.listed_rows_pay, on three CPU ranks over gloo, for every n_ids from 1 to 4000: the
+    ranks' answers are identical (all-gathered) and equal the single-process operator's -- whereas the same rule on each
+    rank's own slice of the item half splits the ranks at some of these batch sizes."""
+    world = 3
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    port = _free_port()
+    procs = [ctx.Process(target=_decision_worker, args=(r, world, port, q)) for r in range(world)]
+    for p in procs:
+        p.start()
+    results = dict(q.get(timeout=180) for _ in range(world))
+    for p in procs:
+        p.join(timeout=60)
+        assert p.exitcode == 0
+    for rank, r in results.items():
+        assert r["new_equal"] and r["new_is_single"], (rank, r)
+        assert r["both"] == (True, True), (rank, r)             # the sweep crosses the threshold
+        assert r["old_split"] > 0, (rank, r)                    # ... where the per-slice rule disagrees between ranks

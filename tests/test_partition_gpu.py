@@ -2,8 +2,10 @@
 refuses two ranks on one device; the driver's 8-GPU run uses backend "nccl" through the same code).
 Checked against the single-GPU HIP result and, through it, the oracle."""
 import os
+import queue
 import socket
 import sys
+import time
 
 import pytest
 import torch
@@ -36,15 +38,38 @@ def _init(rank, world, port, backend):
     return dev
 
 
-def _worker(rank, world, port, q, backend="gloo"):
+# (embedding width, layers): the 64 / 3 of configs[1] and the reference's own training shape, latent_dim 90 with 5 layers --
+# at 90 columns the item half runs the 2-entry sweep (k_sweep_wide), the fused apply of 68..128 columns, the wide listed rows
+SHAPES = [pytest.param(64, 3, id="64-3"), pytest.param(90, 5, id="90-5")]
+# the tests that always ran at 64 / 3 keep their ids; each has a twin at the reference's shape
+REFERENCE_SHAPE = [pytest.param(90, 5, id="90-5")]
+RAMP = {3: (0.4, 0.3, 0.2, 0.1), 5: (0.3, 0.25, 0.15, 0.12, 0.1, 0.08)}      # unequal alphas for the forward workers
+
+
+def _force_sweep(cfg):
+    """cfg["sweep"]: every item half that qualifies at all runs the band sweep (LGCN_SWEEP=1), here a rank's item rows over
+    the columns of its own users [u0, u1) -- a plan whose column range does not start at 0 on every rank but the first."""
+    if cfg.get("sweep"):
+        from gnn_ecommerce_amd import graph as G
+        G.USE_SWEEP = "1"
+
+
+def _sweep_report(op):
+    """What an item operator ran as: (its sweep column range, [(groups, plan groups, plan bands)] of the plans built)."""
+    return op.sweep_cols, [(k, p.dims["groups"], p.dims["n_bands"]) for k, p in op._sweep.items()]
+
+
+def _worker(rank, world, port, q, backend="gloo", cfg=None):
+    cfg = cfg or {}
     dev = _init(rank, world, port, backend)
     try:
         import gnn_ecommerce_amd as lg
         from gnn_ecommerce_amd import synth
         from gnn_ecommerce_amd.partition import PartitionedPropagator
+        _force_sweep(cfg)
         g = synth.make_bipartite(20000, 1500, 150000, seed=3)
         ei, ew = g.coo(dev)
-        n, dim, alphas = g.num_nodes, 64, (0.4, 0.3, 0.2, 0.1)
+        n, dim, alphas = g.num_nodes, cfg.get("dim", 64), RAMP[cfg.get("layers", 3)]
         x0 = synth.xavier_table(n, dim, 2, dev)
         single = lg.propagate_sum(x0, lg.PropGraph(ei, ew, n), alphas)
         pp = PartitionedPropagator(ei, ew, g.n_users, g.n_items, rank, world)
@@ -70,36 +95,67 @@ def _worker(rank, world, port, q, backend="gloo"):
         q.put((rank, {"recorded": rec.recorded, "recorded_same": bool(same),
                       "own": rel(out[lo:hi], single[lo:hi]), "items": rel(out[g.n_users:], single[g.n_users:]),
                       "full": rel(full, single), "worst_row": ((full - single).norm(dim=1) / single.norm(dim=1)).max().item(),
-                      "share": pp.local_nnz / g.nnz, "world": dist.get_world_size(), "backend": dist.get_backend()}))
+                      "share": pp.local_nnz / g.nnz, "world": dist.get_world_size(), "backend": dist.get_backend(),
+                      "range": (lo, hi), "sweep": _sweep_report(pp.item_op)}))
     finally:
         dist.destroy_process_group()
 
 
-def run_ranks(target, world, backend="gloo"):
+def run_ranks(target, world, backend="gloo", cfg=None, timeout=300):
+    """Spawn ``world`` ranks of ``target`` and collect one result per rank.  A rank that dies fails the test within a
+    second or two (its peers may be stuck in a collective with it: they are killed) instead of after ``timeout``."""
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     port = _free_port()
-    procs = [ctx.Process(target=target, args=(r, world, port, q, backend)) for r in range(world)]
+    procs = [ctx.Process(target=target, args=(r, world, port, q, backend, cfg or {})) for r in range(world)]
     for p in procs:
         p.start()
+    results, ok = {}, False
     try:
-        results = dict(q.get(timeout=300) for _ in range(world))
+        deadline = time.monotonic() + timeout
+        while len(results) < world:
+            try:
+                rank, res = q.get(timeout=1.0)
+                results[rank] = res
+                continue
+            except queue.Empty:
+                pass
+            dead = [(r, p.exitcode) for r, p in enumerate(procs) if p.exitcode not in (None, 0)]
+            assert not dead, f"rank(s) died before reporting (rank, exit code): {dead}"
+            assert time.monotonic() < deadline, f"no result from ranks {sorted(set(range(world)) - set(results))} in {timeout} s"
+        ok = True
     finally:
         for p in procs:
-            p.join(timeout=60)
+            p.join(timeout=60 if ok else 5)
             if p.is_alive():
                 p.kill()
+                p.join(timeout=10)
     assert all(p.exitcode == 0 for p in procs), [p.exitcode for p in procs]
     assert sorted(results) == list(range(world))
     return results
 
 
-def test_two_ranks_one_gpu_match_single_gpu(device):
-    results = run_ranks(_worker, 2)
+def _check_forward(results):
     for rank, r in results.items():
         assert r["own"] <= 1e-5 and r["items"] <= 1e-5 and r["full"] <= 1e-5 and r["worst_row"] <= 1e-5, (rank, r)
+        assert r["recorded_same"], (rank, r)
+
+
+def test_two_ranks_one_gpu_match_single_gpu(device):
+    _two_ranks_forward(64, 3)
+
+
+@pytest.mark.parametrize("dim,layers", REFERENCE_SHAPE)
+def test_two_ranks_one_gpu_match_single_gpu_at_the_reference_shape(device, dim, layers):
+    _two_ranks_forward(dim, layers)
+
+
+def _two_ranks_forward(dim, layers):
+    results = run_ranks(_worker, 2, cfg=dict(dim=dim, layers=layers))
+    _check_forward(results)
+    for rank, r in results.items():
         assert 0.45 <= r["share"] <= 0.55
-        assert r["recorded_same"] and not r["recorded"], (rank, r)      # gloo cannot be captured: both ranks went eager, together
+        assert not r["recorded"], (rank, r)      # gloo cannot be captured: both ranks went eager, together
 
 
 def _uses_node(fn, name, depth=6):
@@ -109,15 +165,17 @@ def _uses_node(fn, name, depth=6):
     return name in type(fn).__name__ or any(_uses_node(nxt, name, depth - 1) for nxt, _ in fn.next_functions)
 
 
-def _train_worker(rank, world, port, q, backend="gloo"):
+def _train_worker(rank, world, port, q, backend="gloo", cfg=None):
+    cfg = cfg or {}
     dev = _init(rank, world, port, backend)
     try:
         import gnn_ecommerce_amd as lg
         from gnn_ecommerce_amd import synth
         from gnn_ecommerce_amd.partition import PartitionedPropagator, partitioned_bpr_loss
+        _force_sweep(cfg)
         g = synth.make_bipartite(20000, 1500, 150000, seed=3)
         ei, ew = g.coo(dev)
-        n, dim, layers, decay, batch = g.num_nodes, 64, 3, 1e-4, 1024
+        n, dim, layers, decay, batch = g.num_nodes, cfg.get("dim", 64), cfg.get("layers", 3), 1e-4, 1024
         w0 = synth.xavier_table(n, dim, 2, dev)
         gen = torch.Generator().manual_seed(9)
         users = torch.randperm(g.n_users, generator=gen)[:batch].to(dev)
@@ -127,6 +185,7 @@ def _train_worker(rank, world, port, q, backend="gloo"):
         model = lg.LightGCN(n, dim, layers)
         model.load_state_dict({"alpha": model.alpha, "embedding.weight": w0.cpu()})
         model.to(dev)
+        alphas = model.alpha.tolist()                       # 1 / (K + 1) each, as the model holds it
         labels = torch.stack((torch.cat([users, users]), torch.cat([pos, neg])))
         out = model(ei, labels, ew)
         bpr = model.recommendation_loss(out[:batch], out[batch:], 0) * batch
@@ -150,7 +209,7 @@ def _train_worker(rank, world, port, q, backend="gloo"):
             partition.SEEDED_STEP = seeded
             lg.propagate.SEED_ROWS_FACTOR = 0                   # the seeded node whatever the table size (21,500 rows here)
             wp = w0.clone().requires_grad_(True)
-            local, gbpr, greg = partitioned_bpr_loss(pp, wp, [0.25] * 4, users, pos, neg, decay, zero_foreign_rows=not seeded)
+            local, gbpr, greg = partitioned_bpr_loss(pp, wp, alphas, users, pos, neg, decay, zero_foreign_rows=not seeded)
             res[("seeded_" if seeded else "") + "node"] = _uses_node(local.grad_fn, "PartitionedStep")
             local.backward()
             torch.cuda.synchronize()
@@ -177,7 +236,7 @@ def _train_worker(rank, world, port, q, backend="gloo"):
         tables = {}
         for graphs in (False, True, "full"):
             wt = w0.clone()
-            tr = PartitionedTrainer(pp, wt, [0.25] * 4, lr=0.005, decay=decay, batch=batch, graphs=graphs, warmup=1)
+            tr = PartitionedTrainer(pp, wt, alphas, lr=0.005, decay=decay, batch=batch, graphs=graphs, warmup=1)
             stats = []
             for k in range(4):
                 stats.append(tr.step(torch.roll(users, k), pos, neg).clone())
@@ -197,21 +256,57 @@ def _train_worker(rank, world, port, q, backend="gloo"):
         res["trainer_own"] = rel(first[lo:hi] - w0[lo:hi], ref_w[lo:hi] - w0[lo:hi])
         res["trainer_items"] = rel(first[g.n_users:] - w0[g.n_users:], ref_w[g.n_users:] - w0[g.n_users:])
         res["trainer_bpr"] = abs(tables[False][2][0, 0].item() - bpr.item()) / abs(bpr.item())
+        res["range"], res["listed"] = (lo, hi), pp.listed_rows_pay(4 * batch)
+        res["sweep"], res["sweep_t"] = _sweep_report(pp.item_op), _sweep_report(pp._transposed_ops()[1])
         q.put((rank, res))
     finally:
         dist.destroy_process_group()
 
 
-def test_two_ranks_training_step_matches_single_gpu(device):
-    results = run_ranks(_train_worker, 2)
+def _check_training(results, full_launches=None):
+    """The assertions of a training worker's report, every rank.  ``full_launches``: how many graphs graphs="full" must
+    replay (1 over nccl: the collectives inside); None = the segmented fallback every gloo rank agrees on."""
     for rank, r in results.items():
         assert r["bpr"] <= 1e-5 and r["reg"] <= 1e-5 and r["own"] <= 1e-5 and r["items"] <= 1e-5, (rank, r)
         assert r["seeded_bpr"] <= 1e-5 and r["seeded_reg"] <= 1e-5 and r["seeded_own"] <= 1e-5 and r["seeded_items"] <= 1e-5, (rank, r)
         assert r["seeded_node"] and not r["node"], (rank, r)
         assert r["trainer_graph_equals_eager"] and r["trainer_graph_launches"] >= 2, (rank, r)
-        assert r["trainer_full_equals_eager"] and r["trainer_full_launches"] >= 2, (rank, r)     # gloo: segments, agreed
+        if full_launches is None:
+            assert r["trainer_full_equals_eager"] and r["trainer_full_launches"] >= 2, (rank, r)     # gloo: segments, agreed
+        else:
+            assert r["trainer_full_equals_eager"] and r["trainer_full_launches"] == full_launches, (rank, r)
         assert r["trainer_own"] <= 1e-5 and r["trainer_items"] <= 1e-5 and r["trainer_bpr"] <= 1e-5, (rank, r)
         assert r["adam_own"] <= 1e-5 and r["adam_items"] <= 1e-5 and r["adam_foreign_untouched"], (rank, r)
+        assert r["listed"], (rank, r)          # the listed-rows exchange of the last item step is what ran
+
+
+def test_two_ranks_training_step_matches_single_gpu(device):
+    _check_training(run_ranks(_train_worker, 2, cfg=dict(dim=64, layers=3)))
+
+
+@pytest.mark.parametrize("dim,layers", REFERENCE_SHAPE)
+def test_two_ranks_training_step_matches_single_gpu_at_the_reference_shape(device, dim, layers):
+    """D=90, K=5: the seeded backward's exchanged item blocks must be dense (a padded table's strided view is summed wrong
+    by gloo and refused by RCCL)."""
+    _check_training(run_ranks(_train_worker, 2, cfg=dict(dim=dim, layers=layers)))
+
+
+@pytest.mark.parametrize("dim,layers", SHAPES)
+def test_two_ranks_with_the_item_sweep_on_their_own_user_ranges(device, dim, layers):
+    """LGCN_SWEEP=1 in the ranks: each rank's item half -- forward A and the A^T of the backward pass -- runs the band sweep
+    over the columns [u0, u1) of its own users (rank 1: u0 > 0), at 2 bands (a rank's slice holds ~50 entries per item
+    row); the 2-entry plan at D=90, the 4-entry plan at D=64.  Same gates as the default workers."""
+    groups = 2 if dim == 90 else 4
+    cfg = dict(dim=dim, layers=layers, sweep=True)
+    fwd = run_ranks(_worker, 2, cfg=cfg)
+    _check_forward(fwd)
+    train = run_ranks(_train_worker, 2, cfg=cfg)
+    _check_training(train)
+    for rank, r in list(fwd.items()) + list(train.items()):
+        reports = [r["sweep"]] + ([r["sweep_t"]] if "sweep_t" in r else [])
+        for cols, plans in reports:
+            assert tuple(cols) == tuple(r["range"]) and (rank == 0 or cols[0] > 0), (rank, r)
+            assert plans == [(groups, groups, 2)], (rank, r)
 
 
 def test_exchange_hook_of_the_c_abi_drives_a_partitioned_hop(device):
@@ -335,15 +430,31 @@ def test_eight_ranks_at_full_size_on_one_gpu(device):
     collective a device-side sum across the ranks -- the real kernels on the real slices (each rank's item step runs the
     2-band sweep of its own user range), against the single-GPU path: get_embedding on every rank's rows, then one
     training step (B=1024: seeded node, per-hop exchange, Adam over the rows a rank owns) against the single-GPU step."""
+    _eight_ranks_at_full_size(device, 64, 3)
+
+
+@pytest.mark.parametrize("dim,layers", REFERENCE_SHAPE)
+def test_eight_ranks_at_full_size_on_one_gpu_at_the_reference_shape(device, dim, layers):
+    """The same at the reference's D=90, K=5: every rank's item half sweeps its own user range with the 2-entry plan."""
+    _eight_ranks_at_full_size(device, dim, layers)
+
+
+def _eight_ranks_at_full_size(device, dim, layers, pick_share=None, monkeypatch=None):
+    """The body of the eight-rank test; returns (per-rank results, the partitions, the single-GPU listed-rows choice).
+    ``pick_share(pps, n_ids)``: a LISTED_ROWS_MAX_SHARE for the whole comparison (set through ``monkeypatch`` before the
+    single-GPU step), chosen from the built partitions."""
     import gnn_ecommerce_amd as lg
-    from gnn_ecommerce_amd import synth
+    from gnn_ecommerce_amd import graph as G, synth
     from gnn_ecommerce_amd.partition import PartitionedPropagator, step_backward, step_forward
     from gnn_ecommerce_amd.optim import Adam as HipAdam
-    world, dim, layers, batch, decay = 8, 64, 3, 1024, 1e-4
+    world, batch, decay = 8, 1024, 1e-4
     g = synth.make_bipartite(**synth.CONFIG_COSMETICS, seed=0)
     ei, ew = g.coo(device)
+    torch.cuda.reset_peak_memory_stats(device)                # (after the first allocation: the allocator exists)
     n, nu = g.num_nodes, g.n_users
-    alphas = [0.25] * 4
+    pps = [PartitionedPropagator(ei, ew, nu, g.n_items, r, world) for r in range(world)]
+    if pick_share is not None:
+        monkeypatch.setattr(G, "LISTED_ROWS_MAX_SHARE", pick_share(pps, 4 * batch))
     w0 = synth.xavier_table(n, dim, 0, device)
     gen = torch.Generator().manual_seed(3)
     users = torch.randint(0, nu, (batch,), generator=gen).to(device)
@@ -353,6 +464,7 @@ def test_eight_ranks_at_full_size_on_one_gpu(device):
     model = lg.LightGCN(n, dim, layers)
     model.load_state_dict({"alpha": model.alpha, "embedding.weight": w0.cpu()})
     model.to(device)
+    alphas = model.alpha.tolist()
     with torch.no_grad():
         single = model.get_embedding(ei, ew)
     labels = torch.stack((torch.cat([users, users]), torch.cat([pos, neg])))
@@ -363,7 +475,8 @@ def test_eight_ranks_at_full_size_on_one_gpu(device):
     ref_grad = model.embedding.weight.grad.clone()
     HipAdam([model.embedding.weight], lr=0.005).step()
     ref_w = model.embedding.weight.detach()
-    pps = [PartitionedPropagator(ei, ew, nu, g.n_items, r, world) for r in range(world)]
+    single_listed = lg.get_graph(ei, ew, n).halves()[1].listed_rows_pay(4 * batch)
+    del model, out
     assert sum(pp.local_nnz for pp in pps) == g.nnz and all(pp.item_op.sweep_cols is not None for pp in pps)
 
     def rel(a, b):
@@ -396,11 +509,99 @@ def test_eight_ranks_at_full_size_on_one_gpu(device):
 
     results = _run_thread_ranks(world, rank_body)
     torch.cuda.synchronize()
+    print(f"eight ranks at D={dim} K={layers}: peak device memory {torch.cuda.max_memory_allocated(device) / 2 ** 30:.1f} GiB")
     for rank, r in enumerate(results):
         print(f"rank {rank}: " + "  ".join(f"{k} {v:.1e}" for k, v in r.items()))
         assert r["own"] <= 1e-5 and r["items"] <= 1e-5 and r["worst"] <= 1e-5, (rank, r)
         assert r["bpr"] <= 1e-5 and r["reg"] <= 1e-5 and r["g_own"] <= 1e-5 and r["g_items"] <= 1e-5, (rank, r)
         assert r["w_own"] <= 1e-4 and r["w_items"] <= 1e-4, (rank, r)
+    # every rank's item half ran the band sweep of its own user range: the plan of this width (2 entries per step at 68..96
+    # columns) at the adaptive band count -- the most bands, at least two, that leave SWEEP_PIECE_ENTRIES entries per piece
+    groups = 2 if 64 < dim <= 96 else 4
+    for rank, pp in enumerate(pps):
+        p = pp.item_op.plan
+        n_ent, rows = int(pp.item_op.rowptr[p.row_end]) - int(pp.item_op.rowptr[p.row_begin]), p.row_end - p.row_begin
+        bands = G.SWEEP_CFG["n_bands"]
+        while bands > 2 and n_ent < G.SWEEP_PIECE_ENTRIES * bands * rows:
+            bands //= 2
+        assert pp.item_op.sweep_cols == pp.ranges[rank] and pp.item_op.sweep_bands == bands, rank
+        assert [(k, sp.dims["groups"], sp.dims["n_bands"]) for k, sp in pp.item_op._sweep.items()] == [(groups, groups, bands)], rank
+    return results, pps, single_listed
+
+
+def test_ranks_agree_on_the_listed_rows_exchange_at_the_threshold(device, monkeypatch):
+    """The last item step of a training forward exchanges either the [2B, D] table of the listed item rows or the
+    [n_items, D] item block, by graph.listed_rows_pay.  Each rank's slice of the item half has its own degree moments, so
+    decided on the slice the ranks could choose differently near the threshold and all-reduce tensors of different shapes
+    (a hang or torn item rows over RCCL).  Here the threshold is put between two ranks' break-even shares of the full-size
+    8-way partition at B=1024 -- the old per-slice rule splits the ranks there -- and then: every rank's decision is the
+    single-GPU one, and the forward + step through the eight thread ranks matches the single-GPU step."""
+    from gnn_ecommerce_amd import graph as G
+    picked = {}
+
+    def between_two_ranks(pps, n_ids):
+        local = []                                           # each rank's break-even share, on its OWN slice's moments
+        for pp in pps:
+            p = pp.item_op.plan
+            s1, s2, rows = G.row_stats(pp.item_op.rowptr, p.row_begin, p.row_end)
+            local.append(n_ids / 4.0 * (s2 / s1 + s1 / rows) / s1)
+        srt = sorted(local)
+        assert srt[3] < srt[4], srt
+        picked.update(local=local, share=0.5 * (srt[3] + srt[4]), n_ids=n_ids)
+        return picked["share"]
+
+    results, pps, single_listed = _eight_ranks_at_full_size(device, 64, 3, between_two_ranks, monkeypatch)
+    assert G.LISTED_ROWS_MAX_SHARE == picked["share"]
+    n_ids = picked["n_ids"]
+    old = [share <= picked["share"] for share in picked["local"]]
+    assert any(old) and not all(old), picked                # the per-slice rule splits the ranks at this threshold
+    new = [pp.listed_rows_pay(n_ids) for pp in pps]
+    print(f"threshold {picked['share']:.4f}: per-slice answers {old}, partition {new[0]}, single GPU {single_listed}")
+    assert new == [single_listed] * len(pps)
+
+
+@pytest.mark.parametrize("graphs", [False, True], ids=["eager", "graphs"])
+def test_trainer_step_bumps_the_weight_version(device, graphs):
+    """PartitionedTrainer writes the table with lgc_adam_step_hp, out of autograd's sight: after a step -- eager or
+    replayed -- recommendK on the same parameter must not serve the table it cached before (it keys on ``w._version``,
+    which optim.Adam bumps), but the table of a fresh model loaded with the updated weight."""
+    import gnn_ecommerce_amd as lg
+    from gnn_ecommerce_amd import synth
+    from gnn_ecommerce_amd.partition import PartitionedPropagator
+    from gnn_ecommerce_amd.trainer import PartitionedTrainer
+    g = synth.make_bipartite(6000, 700, 50000, seed=5)
+    ei, ew = g.coo(device)
+    n, nu, ni, dim, layers, batch = g.num_nodes, g.n_users, g.n_items, 64, 3, 256
+    model = lg.LightGCN(n, dim, layers)
+    model.load_state_dict({"alpha": model.alpha, "embedding.weight": synth.xavier_table(n, dim, 1)})
+    model.to(device)
+    pp = PartitionedPropagator(ei, ew, nu, ni, 0, 1)
+    tr = PartitionedTrainer(pp, model.embedding.weight, model.alpha.tolist(), lr=0.05, batch=batch, graphs=graphs, warmup=1)
+    gen = torch.Generator().manual_seed(2)
+    users = torch.randperm(nu, generator=gen)[:batch].to(device)
+    pos = (torch.randint(0, ni, (batch,), generator=gen) + nu).to(device)
+    neg = (torch.randint(0, ni, (batch,), generator=gen) + nu).to(device)
+    asked = users[:8].tolist()                               # users of the batch: their rows move with the step
+    seen = torch.zeros(len(asked), ni)
+    if graphs:
+        tr.step(users, pos, neg)                             # eager warm-up
+        tr.step(users, pos, neg)                             # recorded, replayed once
+        assert tr.graph_launches >= 1
+    with torch.no_grad():
+        before = model.recommendK(ei, ew, nu, ni, seen, asked, 10)
+        cached = model._serving_embedding(ei, ew).clone()
+    version = model.embedding.weight._version
+    tr.step(users, pos, neg)                                 # graphs: a replay
+    torch.cuda.synchronize()
+    assert model.embedding.weight._version > version
+    fresh = lg.LightGCN(n, dim, layers)
+    fresh.load_state_dict({"alpha": model.alpha.cpu(), "embedding.weight": model.embedding.weight.detach().cpu()})
+    fresh.to(device)
+    with torch.no_grad():
+        after, want = model.recommendK(ei, ew, nu, ni, seen, asked, 10), fresh.recommendK(ei, ew, nu, ni, seen, asked, 10)
+        served, want_table = model._serving_embedding(ei, ew), fresh.get_embedding(ei, ew)
+    assert torch.equal(served, want_table) and not torch.equal(served, cached)
+    assert after.equals(want) and not after.equals(before)
 
 
 def test_the_multi_gpu_training_harness_runs_two_ranks_on_one_gpu(device):
