@@ -17,7 +17,7 @@ import torch
 LIB_NAME = "liblgconv_hip.so"
 # LGCN_LIB_PATH selects another build of the SAME library (A/B kernel experiments); never a fallback.
 LIB_PATH = os.environ.get("LGCN_LIB_PATH") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", LIB_NAME)
-ABI_VERSION = 12
+ABI_VERSION = 13
 
 # status bits (include/lgconv_hip.h)
 ST_INDEX_OOB = 1
@@ -55,6 +55,17 @@ class OperatorC(Structure):
                 ("partials", c_void_p), ("sweep", POINTER(SweepArraysC)), ("tiles", TileClassC * 3),
                 ("row_begin", c_int32), ("row_end", c_int32), ("short_max", c_int32), ("n_chunks", c_int32),
                 ("n_multi", c_int32), ("n_tile_classes", c_int32), ("tiles_per_wave", c_int32), ("reserved", c_int32)]
+
+
+# lgc_apply_route's codes (LGC_ROUTE_*; LGC_ROUTE_WT_STORE is the bit 0x100, spelt "+wt" by route_name)
+ROUTES = {1: "rows", 2: "sweep", 3: "sweep_wide", 4: "sweep_two_pass", 5: "fused_dpp", 6: "fused_generic", 7: "split_dpp",
+          8: "split_generic"}
+ROUTE_WT_STORE = 0x100
+
+
+def route_name(code: int) -> str:
+    """"fused_dpp+wt" for LGC_ROUTE_FUSED_DPP | LGC_ROUTE_WT_STORE, "fused_dpp" without the bit."""
+    return ROUTES[code & ~ROUTE_WT_STORE] + ("+wt" if code & ROUTE_WT_STORE else "")
 
 
 EXCHANGE_FN = CFUNCTYPE(c_int, c_void_p, c_int64, c_int64, c_int32, c_void_p, c_void_p)   # lgc_exchange_fn
@@ -105,6 +116,7 @@ SIGNATURES = {
     "lgc_spmm_sweep": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_int32, c_void_p,
                                c_int32, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_float, c_float,
                                c_int32, c_void_p]),
+    "lgc_apply_route": (c_int, [POINTER(OperatorC), c_int64, c_int64, c_int64, c_int64, c_int32]),
     "lgc_apply": (c_int, [POINTER(OperatorC), c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_float, c_float,
                           c_int32, c_void_p]),
     "lgc_hop_exchange": (c_int, [POINTER(OperatorC), POINTER(OperatorC), c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p,

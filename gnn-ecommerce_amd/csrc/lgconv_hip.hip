@@ -2679,7 +2679,9 @@ int sweep_plan_build(lgc_sweep_plan &pl, const int32_t *rowptr, const lgc_entry 
     return 0;
 }
 
-// Tuning switches for A/B runs, read ONCE per process (the launch paths used to call getenv per hop).
+// Tuning switches for A/B runs, read ONCE per process (the launch paths used to call getenv per hop): at the first call
+// that consults them -- the first hop, or the first lgc_apply_route.  Setting LGCN_NO_* later in the same process changes
+// nothing; a test of another switch set runs in a fresh process.
 struct Knobs {
     bool no_fast_tiles, no_fused_apply;
     int64_t sweep_launch_waves;
@@ -2714,6 +2716,23 @@ struct TilePrep {
     int64_t blocks;
 };
 
+// Output rows leave through sc1 buffer stores (store_out) while every byte offset of y fits 32 bits.
+static bool wt_store_ok(int64_t table_rows, int64_t y_stride) { return table_rows * y_stride * 4 < (int64_t(1) << 32); }
+
+static int64_t table_bytes(int64_t table_rows, int64_t stride, int32_t dim) { return ((table_rows - 1) * stride + dim) * 4; }
+
+// Tile fast path: 16-lane rows, 24-bit row ids, 32-bit byte offsets, and the padding id 0xFFFFFF must fall outside
+// every table so that the hardware's range check turns padding into "load zeros / drop the store".  r_stride 0: no r.
+static bool tiles_fast_ok(bool has_meta, int32_t dim, int64_t table_rows, int64_t x_stride, int64_t y_stride, int64_t r_stride) {
+    auto pad_is_oob = [&](int64_t stride) {
+        const uint32_t pad = (uint32_t)(0xFFFFFFull * (uint64_t)(stride * 4));
+        return stride * 4 < (1 << 24) && table_bytes(table_rows, stride, dim) < (int64_t(1) << 32) &&
+               (int64_t)pad >= table_bytes(table_rows, stride, dim);
+    };
+    return has_meta && ((dim >= 61 && dim <= 64) || (dim >= 68 && dim <= 128)) && table_rows > 0 && table_rows < 0xFFFFFF &&
+           pad_is_oob(x_stride) && pad_is_oob(y_stride) && (r_stride == 0 || pad_is_oob(r_stride)) && !knobs().no_fast_tiles;
+}
+
 int prepare_tiles(TilePrep &out, const int32_t *order, const int32_t *meta, const lgc_entry *slab, int32_t n_tiles, int32_t width,
                   int32_t tiles_per_wave, int64_t table_rows, const float *x, int64_t x_stride, float *y,
                   int64_t y_stride, const float *r, int64_t r_stride, float a, float b, int32_t dim) {
@@ -2731,24 +2750,15 @@ int prepare_tiles(TilePrep &out, const int32_t *order, const int32_t *meta, cons
     p.n_tiles = n_tiles; p.tiles_per_wave = tiles_per_wave;
     p.dim = dim;
     p.lpr = (dim + 3) / 4;
-    p.wt_store = (table_rows * y_stride * 4 < (int64_t(1) << 32)) ? 1 : 0;
+    p.wt_store = wt_store_ok(table_rows, y_stride) ? 1 : 0;
     p.meta = meta;
     const int64_t waves = ((int64_t)n_tiles + tiles_per_wave - 1) / tiles_per_wave;
     out.blocks = (waves + 3) / 4;
-    // fast path: 16-lane rows, 24-bit row ids, 32-bit byte offsets, and the padding id 0xFFFFFF must fall outside
-    // every table so that the hardware's range check turns padding into "load zeros / drop the store"
-    auto table_bytes = [&](int64_t stride) { return ((table_rows - 1) * stride + dim) * 4; };
-    auto pad_is_oob = [&](int64_t stride) {
-        const uint32_t pad = (uint32_t)(0xFFFFFFull * (uint64_t)(stride * 4));
-        return stride * 4 < (1 << 24) && table_bytes(stride) < (int64_t(1) << 32) && (int64_t)pad >= table_bytes(stride);
-    };
-    out.fast = meta != nullptr && ((dim >= 61 && dim <= 64) || (dim >= 68 && dim <= 128)) && table_rows > 0 &&
-               table_rows < 0xFFFFFF &&
-               pad_is_oob(x_stride) && pad_is_oob(y_stride) && (!r || pad_is_oob(r_stride)) && !knobs().no_fast_tiles;
+    out.fast = tiles_fast_ok(meta != nullptr, dim, table_rows, x_stride, y_stride, r ? r_stride : 0);
     if (out.fast) {
-        p.x_bytes = (uint32_t)table_bytes(x_stride);
-        p.y_bytes = (uint32_t)table_bytes(y_stride);
-        p.r_bytes = r ? (uint32_t)table_bytes(r_stride) : 0u;
+        p.x_bytes = (uint32_t)table_bytes(table_rows, x_stride, dim);
+        p.y_bytes = (uint32_t)table_bytes(table_rows, y_stride, dim);
+        p.r_bytes = r ? (uint32_t)table_bytes(table_rows, r_stride, dim) : 0u;
     }
     out.p = p;
     return 0;
@@ -3013,7 +3023,7 @@ int lgc_spmm(const int32_t *rowptr, const lgc_entry *entries, int32_t row_begin,
     SpmmArgs p{rowptr, entries, x, y, r, x_stride, y_stride, r_stride, a, b, dim, cfg.lpr, row_begin, row_end,
                short_max, 0};
     // write-through output stores address y with 32-bit byte offsets
-    p.wt_store = (table_rows * y_stride * 4 < (int64_t(1) << 32)) ? 1 : 0;
+    p.wt_store = wt_store_ok(table_rows, y_stride) ? 1 : 0;
     const int waves_per_block = kBlock / kWave;
     const int rows_per_wave = kWave / cfg.lpr;
     return dispatch_dim(cfg, [&](auto vec) -> int {
@@ -3100,7 +3110,9 @@ int lgc_bipartite_split(const int64_t *edge_index, int64_t n_edges, int64_t *out
 static size_t row_plan_ws(void *base, int64_t n, int32_t **a, int32_t **b, int32_t **c, void **cub, size_t *cub_bytes) {
     size_t cb = 0;
     int32_t *nul = nullptr;
-    (void)hipcub::DeviceScan::ExclusiveSum(nullptr, cb, nul, nul, (int)std::max<int64_t>(n, 1), (hipStream_t)0);
+    // sized for the n + 1 elements lgc_row_plan_count scans (sized for n, the scan refused ranges of 2^23 and 2^24 rows
+    // with hipErrorInvalidValue: its scratch was too small)
+    (void)hipcub::DeviceScan::ExclusiveSum(nullptr, cb, nul, nul, (int)(n + 1), (hipStream_t)0);
     const uintptr_t p = reinterpret_cast<uintptr_t>(base);
     const size_t arr = align_up((size_t)(n + 1) * 4, 256);
     if (a) *a = reinterpret_cast<int32_t *>(p);
@@ -3674,7 +3686,7 @@ int lgc_spmm_sweep(const uint32_t *slabs, const int32_t *wave_slab_ptr, const in
     DimCfg cfg;
     dim_cfg(dim, &cfg);
     SpmmArgs sp{nullptr, nullptr, x, y, r, x_stride, y_stride, r_stride, a, b, dim, cfg.lpr, 0, 0, 0, 0};
-    sp.wt_store = (table_rows * y_stride * 4 < (int64_t(1) << 32)) ? 1 : 0;
+    sp.wt_store = wt_store_ok(table_rows, y_stride) ? 1 : 0;
     if (n_wide + n_rows > 0) {
         const int rows_per_block = (kBlock / kWave) * (kWave / cfg.lpr);
         hipLaunchKernelGGL((k_sweep_combine<4>), dim3(n_wide + ceil_div(n_rows, rows_per_block)), dim3(kBlock), 0, stream, sp,
@@ -3683,33 +3695,59 @@ int lgc_spmm_sweep(const uint32_t *slabs, const int32_t *wave_slab_ptr, const in
     return (int)hipGetLastError();
 }
 
+int lgc_apply_route(const lgc_operator *op, int64_t table_rows, int64_t x_stride, int64_t y_stride, int64_t r_stride,
+                    int32_t dim) {
+    if (!op || op->n_tile_classes < 0 || op->n_tile_classes > 3) return LGC_E_INVAL;
+    DimCfg cfg;
+    if (!dim_cfg(dim, &cfg)) return LGC_E_DIM;
+    if (table_rows < 0 || x_stride < dim || y_stride < dim || r_stride < 0 || (r_stride > 0 && r_stride < dim)) return LGC_E_INVAL;
+    const int wt = wt_store_ok(table_rows, y_stride) ? LGC_ROUTE_WT_STORE : 0;
+    if (op->sweep) {
+        const int groups = op->sweep->groups ? op->sweep->groups : 4;
+        if (lgc_sweep_ok(dim, table_rows, x_stride) == groups)
+            return wt | (groups == 2 ? LGC_ROUTE_SWEEP_WIDE : dim > 64 ? LGC_ROUTE_SWEEP_TWO_PASS : LGC_ROUTE_SWEEP);
+    }
+    if (op->n_tile_classes == 0 || dim < 4) return wt | LGC_ROUTE_ROWS;
+    bool fast = true;   // one kernel body for every tile class: the DPP one only if each class that has tiles may take it
+    for (int c = 0; c < op->n_tile_classes; ++c)
+        if (op->tiles[c].n_tiles != 0)
+            fast = fast && tiles_fast_ok(op->tiles[c].meta != nullptr, dim, table_rows, x_stride, y_stride, r_stride);
+    if (knobs().no_fused_apply) return wt | (fast ? LGC_ROUTE_SPLIT_DPP : LGC_ROUTE_SPLIT_GENERIC);
+    return wt | (fast ? LGC_ROUTE_FUSED_DPP : LGC_ROUTE_FUSED_GENERIC);
+}
+
 int lgc_apply(const lgc_operator *op, int64_t table_rows, const float *x, int64_t x_stride, float *y, int64_t y_stride,
               const float *r, int64_t r_stride, float a, float b, int32_t dim, void *stream) {
-    if (!op || op->n_tile_classes < 0 || op->n_tile_classes > 3) return LGC_E_INVAL;
-    if (op->sweep && lgc_sweep_ok(dim, table_rows, x_stride) == (op->sweep->groups ? op->sweep->groups : 4)) {
+    const int route = lgc_apply_route(op, table_rows, x_stride, y_stride, r ? r_stride : 0, dim);
+    if (route < 0) return route;
+    if (r && r_stride < dim) return LGC_E_INVAL;
+    switch (route & ~LGC_ROUTE_WT_STORE) {
+    case LGC_ROUTE_SWEEP:
+    case LGC_ROUTE_SWEEP_WIDE:
+    case LGC_ROUTE_SWEEP_TWO_PASS: {
         const lgc_sweep_arrays *sw = op->sweep;
         return lgc_spmm_sweep(sw->slabs, sw->wave_slab_ptr, sw->wave_npieces, sw->piece_slot, sw->n_waves, sw->row_cap,
                               sw->groups, sw->multi, sw->n_rows, sw->multi_wide, sw->n_wide, sw->partials, table_rows, x, x_stride, y,
                               y_stride, r, r_stride, a, b, dim, stream);
     }
-    const bool tiled = op->n_tile_classes > 0 && dim >= 4;
-    if (tiled && !knobs().no_fused_apply) {
+    case LGC_ROUTE_FUSED_DPP:
+    case LGC_ROUTE_FUSED_GENERIC: {
         // one launch: [chunk workgroups | tile classes], then the fixed-order combine of rows cut into several chunks
         DimCfg cfg;
-        if (!dim_cfg(dim, &cfg)) return LGC_E_DIM;
-        if (!x || !y || x == y || x_stride < dim || y_stride < dim || (r && r_stride < dim) || op->n_chunks < 0 || op->n_multi < 0 ||
+        dim_cfg(dim, &cfg);
+        if (!x || !y || x == y || op->n_chunks < 0 || op->n_multi < 0 ||
             (op->n_chunks > 0 && (!op->chunks || !op->rowptr || !op->entries)) || (op->n_multi > 0 && (!op->multi || !op->partials)))
             return LGC_E_INVAL;
         FusedArgs f{};
         f.sp = SpmmArgs{op->rowptr, op->entries, x, y, r, x_stride, y_stride, r_stride, a, b, dim, cfg.lpr, op->row_begin,
                         op->row_begin, op->short_max, 0};
-        f.sp.wt_store = (table_rows * y_stride * 4 < (int64_t(1) << 32)) ? 1 : 0;
+        f.sp.wt_store = (route & LGC_ROUTE_WT_STORE) ? 1 : 0;
         f.chunks = op->chunks;
         f.partials = op->partials;
         f.n_chunks = op->n_chunks;
         f.chunk_blocks = op->n_chunks > 0 ? ceil_div(op->n_chunks, kBlock / kWave) : 0;
         int64_t total = f.chunk_blocks;
-        bool fast = true;
+        const bool fast = (route & ~LGC_ROUTE_WT_STORE) == LGC_ROUTE_FUSED_DPP;
         for (int c = op->n_tile_classes - 1; c >= 0; --c) {   // widest class first: its wavefronts run longest (a rank of
             const lgc_tile_class &tc = op->tiles[c];          // an 8-way partition: 113 vs 116 us per hop)
             TilePrep tp;
@@ -3718,7 +3756,6 @@ int lgc_apply(const lgc_operator *op, int64_t table_rows, const float *x, int64_
                                          r, r_stride, a, b, dim);
             if (rc != 0) return rc;
             if (tc.n_tiles == 0) continue;
-            fast = fast && tp.fast;
             f.t[f.n_classes] = tp.p;
             f.width[f.n_classes] = tc.width;
             f.blocks[f.n_classes] = (int32_t)tp.blocks;
@@ -3736,6 +3773,12 @@ int lgc_apply(const lgc_operator *op, int64_t table_rows, const float *x, int64_
                                op->n_multi, op->partials);
         return (int)hipGetLastError();
     }
+    default:
+        break;
+    }
+    // LGC_ROUTE_ROWS: lgc_spmm's row part over [row_begin, row_end); LGC_ROUTE_SPLIT_*: its chunks, then every tile class
+    // through lgc_spmm_tiles (whose prepare_tiles takes the DPP body under the same tiles_fast_ok)
+    const bool tiled = (route & ~LGC_ROUTE_WT_STORE) != LGC_ROUTE_ROWS;
     if (!tiled || op->n_chunks > 0) {   // long rows first (they run longest); with tiles the row part gets an empty range
         const int rc = lgc_spmm(op->rowptr, op->entries, op->row_begin, tiled ? op->row_begin : op->row_end, op->short_max,
                                 op->chunks, op->n_chunks, op->multi, op->n_multi, op->partials, table_rows, x, x_stride, y,

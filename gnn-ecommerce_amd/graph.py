@@ -601,9 +601,7 @@ class Operator:
         self._c_structs[key] = keep
         return c
 
-    def apply(self, x: Tensor, out: Tensor, a: float = 1.0, r: Optional[Tensor] = None, b: float = 0.0) -> Tensor:
-        """out[row] = a * (A x)[row] + b * r[row] for the rows of the plan: one ``lgc_apply`` on the current stream."""
-        import ctypes
+    def _apply_args(self, x: Tensor, out: Tensor, r: Optional[Tensor]):
         _check_table(x, "x")
         _check_table(out, "out")
         dim = x.size(1)
@@ -618,7 +616,21 @@ class Operator:
             raise _native.NativeLibraryError(f"embedding width {dim} is not supported by the HIP kernels")
         table_rows = min(x.size(0), out.size(0))
         sweep = sweep_choice(lib, dim, table_rows, x.stride(0)) if self.sweep_cols is not None else 0
-        c = self.c_struct(dim, sweep)
+        return lib, self.c_struct(dim, sweep), dim, table_rows
+
+    def route(self, x: Tensor, out: Tensor, r: Optional[Tensor] = None) -> str:
+        """The kernels ``apply(x, out, r=r)`` would launch, as ``lgc_apply_route`` names them: "fused_dpp", "sweep_wide",
+        ... with "+wt" while the output rows leave through write-through stores.  Launches nothing."""
+        import ctypes
+        lib, c, dim, table_rows = self._apply_args(x, out, r)
+        code = lib.lgc_apply_route(ctypes.byref(c), table_rows, x.stride(0), out.stride(0), 0 if r is None else r.stride(0), dim)
+        _native.check(min(code, 0), "lgc_apply_route")
+        return _native.route_name(code)
+
+    def apply(self, x: Tensor, out: Tensor, a: float = 1.0, r: Optional[Tensor] = None, b: float = 0.0) -> Tensor:
+        """out[row] = a * (A x)[row] + b * r[row] for the rows of the plan: one ``lgc_apply`` on the current stream."""
+        import ctypes
+        lib, c, dim, table_rows = self._apply_args(x, out, r)
         with torch.cuda.device(x.device):
             code = lib.lgc_apply(ctypes.byref(c), table_rows, _native.ptr(x), x.stride(0), _native.ptr(out), out.stride(0),
                                  _native.ptr(r), 0 if r is None else r.stride(0), float(a), float(b), dim,

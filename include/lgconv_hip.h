@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define LGC_ABI_VERSION 12
+#define LGC_ABI_VERSION 13
 
 /* argument errors (negative return values) */
 #define LGC_E_INVAL      (-1)  /* null pointer, negative size, bad flag                    */
@@ -326,6 +326,27 @@ int lgc_spmm_sweep(const uint32_t *slabs, const int32_t *wave_slab_ptr, const in
  * sweep if `sweep` is set and lgc_sweep_ok(dim, table_rows, x_stride); else chunks + tiles; tiles need dim >= 4,
  * narrower tables take lgc_spmm's row part over [row_begin, row_end)).
  *
+ * lgc_apply_route answers, on the host and without launching anything, which of these routes lgc_apply takes for a
+ * table geometry (lgc_apply decides by calling it): one LGC_ROUTE_* code, with LGC_ROUTE_WT_STORE OR-ed in while
+ * y's byte offsets fit 32 bits (table_rows * y_stride * 4 < 2^32: output rows leave through write-through buffer
+ * stores; plain stores beyond), or LGC_E_*.  r_stride = 0: no r.  Only `op` and the HOST struct `op->sweep` are read.
+ * The DPP tile bodies and the sweep need 24-bit row ids, 32-bit byte offsets and the padding id 0xFFFFFF's wrapped
+ * offset beyond the table, so the route depends on table_rows and the strides, not on the width alone.
+ * The switches LGCN_NO_FAST_TILES (no DPP tile bodies) and LGCN_NO_FUSED_APPLY (chunks and tile classes as separate
+ * launches) and LGCN_SWEEP_LAUNCH_WAVES (the sweep in launches of that many wavefronts) are read from the environment
+ * ONCE per process, at the first hop or route query; later changes to the environment are not seen.
+ */
+#define LGC_ROUTE_ROWS           1   /* lgc_spmm's rows: no tile classes, or dim < 4                                 */
+#define LGC_ROUTE_SWEEP          2   /* band sweep, 4 entries per step (61..64 columns) + fixed-order combine        */
+#define LGC_ROUTE_SWEEP_WIDE     3   /* band sweep, 2 entries per step (68..96 columns) + combine                    */
+#define LGC_ROUTE_SWEEP_TWO_PASS 4   /* the 4-entry sweep over columns [0, 64) and [64, dim) (97..128) + combine     */
+#define LGC_ROUTE_FUSED_DPP      5   /* one launch of chunks + tile classes, DPP tile bodies (61..64, 68..128)       */
+#define LGC_ROUTE_FUSED_GENERIC  6   /* one launch of chunks + tile classes, generic tile body                      */
+#define LGC_ROUTE_SPLIT_DPP      7   /* LGCN_NO_FUSED_APPLY: lgc_spmm's chunks, then lgc_spmm_tiles per class, DPP  */
+#define LGC_ROUTE_SPLIT_GENERIC  8   /* LGCN_NO_FUSED_APPLY, generic tile body                                       */
+#define LGC_ROUTE_WT_STORE   0x100   /* bit: output rows through sc1 buffer stores with 32-bit offsets               */
+
+/*
  * lgc_hop_exchange is one LGConv layer (src/lightgcn.py:96) of a user|item graph PARTITIONED over several devices
  * (SURVEY.md 8e): item step (partial sums of all item rows from this rank's own users) -> `exchange(block, rows,
  * row_stride, dim, stream, user)` -> user step (this rank's users from the replicated, now reduced, item rows).
@@ -365,6 +386,8 @@ typedef struct lgc_operator {
     int32_t row_begin, row_end, short_max, n_chunks, n_multi, n_tile_classes, tiles_per_wave, reserved;
 } lgc_operator;
 
+int lgc_apply_route(const lgc_operator *op, int64_t table_rows, int64_t x_stride, int64_t y_stride, int64_t r_stride,
+                    int32_t dim);
 int lgc_apply(const lgc_operator *op, int64_t table_rows, const float *x, int64_t x_stride, float *y, int64_t y_stride,
               const float *r, int64_t r_stride, float a, float b, int32_t dim, void *stream);
 

@@ -1,0 +1,158 @@
+"""One switch set of lgc_apply's hop dispatcher, in a process of its own.
+
+LGCN_NO_FAST_TILES, LGCN_NO_FUSED_APPLY and LGCN_SWEEP_LAUNCH_WAVES are read once per process, at the first hop, so a
+test cannot flip them in its own process: ``tests/test_routes_gpu.py`` starts this script once per switch set, with the
+switches in its environment, and reads the JSON summary it writes to ``--out``.  Every check is an assert: a failing
+one ends the process with a non-zero status and the traceback on stderr.
+
+For every width the child asserts the route ``Operator.route`` reports, compares the tiled operator (whatever tile body
+and launch split the switches give) with the row-pointer path bit for bit, with and without the a / r / b epilogue,
+checks both against an fp64 host evaluation of the same CSR values, and repeats the hop on strided tables whose padding
+columns hold NaN (x, r) and a sentinel bit pattern (y).  The item half runs as a band sweep (forced on); the digests of
+its outputs go into the summary, so that the parent can compare one sweep launch with several.
+"""
+import argparse
+import hashlib
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, "tests")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+import torch  # noqa: E402
+
+from conftest import rel_fro, worst_row_rel  # noqa: E402
+from gnn_ecommerce_amd import graph as G, synth  # noqa: E402
+from gnn_ecommerce_amd.graph import Operator, PropGraph  # noqa: E402
+
+WIDTHS = (61, 64, 68, 80, 90, 96, 101, 128)
+PADS = (1, 3, 8)                  # stride = dim + pad: dim + 1 and dim + 3 give rows that are not 16-byte aligned
+SENTINEL = 0x7FA5A5A5             # a NaN bit pattern no kernel produces
+TOL = 1e-5
+
+
+def fp64_hop(op, x, a=1.0, r=None, b=0.0):
+    """a * A x + b * r over the operator's rows [row_begin, row_end), in fp64 on the host from the operator's own fp32
+    CSR values."""
+    lo, hi = op.plan.row_begin, op.plan.row_end
+    rowptr = op.rowptr.cpu().long()
+    ent = op.entries[rowptr[lo]:rowptr[hi]].cpu()
+    cols, vals = ent[:, 0].long(), ent[:, 1].contiguous().view(torch.float32).double()
+    rows = torch.repeat_interleave(torch.arange(hi - lo), rowptr[lo + 1:hi + 1] - rowptr[lo:hi])
+    y = torch.zeros((hi - lo, x.size(1)), dtype=torch.float64)
+    y.index_add_(0, rows, vals.view(-1, 1) * x.cpu().double()[cols])
+    y = a * y
+    if r is not None:
+        y += b * r[lo:hi].cpu().double()
+    return y
+
+
+def close(got, want, what):
+    e, w = rel_fro(got, want), worst_row_rel(got, want)
+    assert e <= TOL and w <= TOL, (what, e, w)
+
+
+def sentinel_table(n, stride, device):
+    return torch.full((n, stride), SENTINEL, dtype=torch.int32, device=device).view(torch.float32)
+
+
+def nan_padded(t, pad):
+    full = torch.full((t.size(0), t.size(1) + pad), float("nan"), device=t.device)
+    full[:, :t.size(1)] = t
+    return full[:, :t.size(1)]
+
+
+def bits(t):
+    return t.contiguous().view(torch.int32)
+
+
+def digest(t):
+    return hashlib.sha256(t.contiguous().cpu().numpy().tobytes()).hexdigest()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", required=True)
+    args = ap.parse_args()
+    dev = torch.device("cuda:0")
+    fused = os.environ.get("LGCN_NO_FUSED_APPLY") is None
+    fast = os.environ.get("LGCN_NO_FAST_TILES") is None
+    tile_route = ("fused_" if fused else "split_") + ("dpp" if fast else "generic") + "+wt"
+    sweep_route = {61: "sweep", 64: "sweep", 101: "sweep_two_pass", 128: "sweep_two_pass"}
+
+    g = synth.make_bipartite(3000, 400, 30000, 21)       # small_graph(21, 3000, 400, 30000) of test_parity_gpu.py
+    ei, ew = g.coo()
+    n, nu = g.num_nodes, g.n_users
+    op = PropGraph(ei.to(dev), ew.to(dev), n).forward_op
+    plain = Operator.build(n, op.rowptr, op.entries, 0, n, 32, 256, tiles=False)
+    tiled = {mode: None for mode in ("cold", "natural")}
+    for mode in tiled:
+        G.TILE_ORDER = mode
+        tiled[mode] = Operator.build(n, op.rowptr, op.entries, 0, n, 32, 256, tiles=True)
+        assert tiled[mode].tiled and {tc.width for tc in tiled[mode].tiles} <= {8, 16, 32}
+    assert plain.plan.n_chunks > 0 and plain.plan.n_multi > 0, "the graph must have chunked and multi-chunk rows"
+    G.USE_SWEEP = "1"
+    sw = Operator.build(n, op.rowptr, op.entries, nu, n, 32, 256, sweep_cols=(0, nu))
+    assert sw.sweep_cols == (0, nu)
+
+    summary = {"tile_route": tile_route, "widths": {}}
+    for dim in WIDTHS:
+        x = synth.xavier_table(n, dim, 3, dev)
+        r = synth.xavier_table(n, dim, 4, dev)
+        empty = torch.empty_like(x)
+        assert plain.route(x, empty) == plain.route(x, empty, r) == "rows+wt"
+        want = plain.apply(x, torch.empty_like(x))
+        want_r = plain.apply(x, torch.empty_like(x), a=0.75, r=r, b=0.3)
+        close(want.cpu(), fp64_hop(plain, x), ("rows", dim))
+        close(want_r.cpu(), fp64_hop(plain, x, 0.75, r, 0.3), ("rows epilogue", dim))
+        for mode, top in tiled.items():
+            assert top.route(x, empty) == top.route(x, empty, r) == tile_route, (mode, dim, top.route(x, empty))
+            got = top.apply(x, torch.full_like(x, float("nan")))
+            got_r = top.apply(x, torch.full_like(x, float("nan")), a=0.75, r=r, b=0.3)
+            assert torch.equal(got, want) and torch.equal(got_r, want_r), (tile_route, mode, dim)
+        top = tiled["cold"]
+        for pad in PADS:
+            xs, rs = nan_padded(x, pad), nan_padded(r, pad)
+            ys_full = sentinel_table(n, dim + pad, dev)
+            ys = ys_full[:, :dim]
+            assert top.route(xs, ys, rs) == tile_route, (dim, pad, top.route(xs, ys, rs))
+            top.apply(xs, ys)
+            assert torch.equal(ys, want), (tile_route, "strided", dim, pad)
+            top.apply(xs, ys, a=0.75, r=rs, b=0.3)
+            assert torch.equal(ys, want_r), (tile_route, "strided epilogue", dim, pad)
+            assert (bits(ys_full[:, dim:]) == SENTINEL).all(), (tile_route, "padding of y written", dim, pad)
+
+        # the item half as a band sweep: rows [0, nu) are outside the operator and must keep their bits
+        want_sweep = sweep_route.get(dim, "sweep_wide") + "+wt"
+        y = sentinel_table(n, dim, dev)
+        assert sw.route(x, y) == sw.route(x, y, r) == want_sweep, (dim, sw.route(x, y))
+        sw.apply(x, y)
+        ye = sentinel_table(n, dim, dev)
+        sw.apply(x, ye, a=0.75, r=r, b=0.3)
+        close(y[nu:].cpu(), fp64_hop(sw, x), ("sweep", dim))
+        close(ye[nu:].cpu(), fp64_hop(sw, x, 0.75, r, 0.3), ("sweep epilogue", dim))
+        assert (bits(y[:nu]) == SENTINEL).all() and (bits(ye[:nu]) == SENTINEL).all(), ("sweep wrote outside its rows", dim)
+        for pad in PADS:
+            xs, rs = nan_padded(x, pad), nan_padded(r, pad)
+            ys_full = sentinel_table(n, dim + pad, dev)
+            ys = ys_full[:, :dim]
+            assert sw.route(xs, ys, rs) == want_sweep, (dim, pad, sw.route(xs, ys, rs))
+            sw.apply(xs, ys)
+            assert torch.equal(ys[nu:], y[nu:]), ("sweep strided", dim, pad)
+            sw.apply(xs, ys, a=0.75, r=rs, b=0.3)
+            assert torch.equal(ys[nu:], ye[nu:]), ("sweep strided epilogue", dim, pad)
+            assert (bits(ys_full[:nu]) == SENTINEL).all() and (bits(ys_full[:, dim:]) == SENTINEL).all(), \
+                ("sweep wrote outside its rows or columns", dim, pad)
+        groups = 2 if 64 < dim <= 96 else 4
+        summary["widths"][str(dim)] = {"sweep": digest(y[nu:]), "sweep_epilogue": digest(ye[nu:]),
+                                       "sweep_waves": int(sw._sweep[groups].dims["n_waves"])}
+    torch.cuda.synchronize()
+    with open(args.out, "w") as f:
+        json.dump(summary, f)
+
+
+if __name__ == "__main__":
+    main()

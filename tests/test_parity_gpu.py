@@ -713,8 +713,10 @@ def test_end_to_end_caller_loop_learns(device):
 
 @pytest.mark.parametrize("dim", [64, 63, 61, 60, 90, 16, 7, 4, 128, 68, 80, 96, 101, 67])
 def test_tiled_rows_are_bit_identical_to_the_row_pointer_path(device, dim, monkeypatch):
-    """lgc_spmm_tiles (processing order, 1 KiB tiles, DPP fast path at 61..64) vs lgc_spmm's plain row part:
-    same entries in the same order, products rounded before the add -> the same bits, with and without epilogue."""
+    """lgc_spmm_tiles (processing order, 1 KiB tiles, DPP fast path at 61..64 and 68..128) vs lgc_spmm's plain row
+    part: same entries in the same order, products rounded before the add -> the same bits, with and without epilogue.
+    The generic tile body at the DPP widths (LGCN_NO_FAST_TILES, read once per process) runs in a fresh process:
+    tests/test_routes.py::test_forced_route_in_a_fresh_process."""
     from gnn_ecommerce_amd.graph import Operator
     g, ei, ew = small_graph(21, 3000, 400, 30000)
     n = g.num_nodes
@@ -723,21 +725,18 @@ def test_tiled_rows_are_bit_identical_to_the_row_pointer_path(device, dim, monke
     x = synth.xavier_table(n, dim, 3, device)
     r = synth.xavier_table(n, dim, 4, device)
     plain = Operator.build(n, op.rowptr, op.entries, 0, n, 32, 256, tiles=False)
-    assert not plain.tiled
+    assert not plain.tiled and plain.route(x, torch.empty_like(x)) == "rows+wt"
     want = plain.apply(x, torch.empty_like(x))
     want_r = plain.apply(x, torch.empty_like(x), a=0.75, r=r, b=0.3)
+    route = ("fused_dpp" if (61 <= dim <= 64 or 68 <= dim <= 128) else "fused_generic") + "+wt"
     for mode in ("cold", "natural"):
         monkeypatch.setattr("gnn_ecommerce_amd.graph.TILE_ORDER", mode)
         tiled = Operator.build(n, op.rowptr, op.entries, 0, n, 32, 256, tiles=True)
         assert tiled.tiled and {tc.width for tc in tiled.tiles} <= {8, 16, 32}
-        for no_fast in ("", "1"):
-            if no_fast:
-                monkeypatch.setenv("LGCN_NO_FAST_TILES", "1")
-            else:
-                monkeypatch.delenv("LGCN_NO_FAST_TILES", raising=False)
-            got = tiled.apply(x, torch.full_like(x, float("nan")))
-            got_r = tiled.apply(x, torch.full_like(x, float("nan")), a=0.75, r=r, b=0.3)
-            assert torch.equal(got, want) and torch.equal(got_r, want_r), (mode, no_fast)
+        assert tiled.route(x, torch.empty_like(x)) == tiled.route(x, torch.empty_like(x), r) == route, mode
+        got = tiled.apply(x, torch.full_like(x, float("nan")))
+        got_r = tiled.apply(x, torch.full_like(x, float("nan")), a=0.75, r=r, b=0.3)
+        assert torch.equal(got, want) and torch.equal(got_r, want_r), mode
     # a strided (padded) table takes the same path
     wide = torch.zeros((n, dim + 8), device=device)
     xs, ys = wide[:, :dim], torch.zeros((n, dim + 8), device=device)[:, :dim]
