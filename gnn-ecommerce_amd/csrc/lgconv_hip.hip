@@ -16,35 +16,25 @@
 //       row part     rows with <= short_max entries, one lane group per row, entry order, entries
 //                    fetched through a fixed-width slab of row heads
 //   k_spmm_combine   fixed-order sum of a long row's partial slots + epilogue
-//   k_lincomb, k_pair_dot, k_pair_dot_bwd
-#include <hip/hip_runtime.h>
+//   k_rows_tile*, k_sweep*, k_apply_fused: rows of up to 32 entries in tiles, the band sweep, one launch per hop
+//   k_lincomb
+// This unit holds everything that decides which bytes a hop moves (graph build, the row / tile / sweep planners, the hop
+// kernels and their dispatcher); the training glue is lgconv_train.hip, the serving tail and the sampler lgconv_serve.hip.
 #include <hipcub/hipcub.hpp>
 
-#include <cmath>
-#include <cstdint>
 #include <cstdlib>
 #include <cstdio>
 #include <cstring>
-#include <algorithm>
 #include <chrono>
 #include <new>
 #include <thread>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
-#include "lgconv_hip.h"
+#include "lgconv_common.h"
 
 namespace {
-
-constexpr int kWave = 64;
-constexpr int kBlock = 256;  // 4 wavefronts, one per SIMD of a CU
-
-typedef float f4 __attribute__((ext_vector_type(4)));
-// Row slices are only dword-aligned in general (D = 90 -> 360-byte rows; the overlapping last lane):
-// tell the compiler, it still emits global_load_dwordx4 (gfx950 allows dword-aligned wide accesses).
-typedef f4 f4u __attribute__((aligned(4)));
-
-inline int ceil_div(long a, long b) { return (int)((a + b - 1) / b); }
-inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
 
 // ----------------------------------------------------------------------------------------
 // Graph build
@@ -262,7 +252,6 @@ __device__ __forceinline__ void store_row(float *p, const Acc<VEC> &o) {
 // XCD's 4 MiB L2, where 0.42 GB of output per layer evicts the gathered rows (the only data with reuse);
 // an sc1 (write-through) store drops the line from L2 instead (MI355X_MICROARCH.md, table of store
 // flavours).  Needs a buffer descriptor: 32-bit byte offsets, so only for tables below 4 GiB (wt_store).
-typedef unsigned int u4 __attribute__((ext_vector_type(4)));
 template <int VEC, class P>
 __device__ __forceinline__ void store_out(const P &p, int64_t row, int c0, const Acc<VEC> &o) {
     if constexpr (VEC == 4) {
@@ -855,6 +844,17 @@ __device__ __forceinline__ void tiles_body(const TileArgs &p, const int64_t bloc
     }
 }
 
+// The three tile classes -- rows of up to W = 8 / 16 / 32 entries, fetched with L = 1 / 1 / 2 loads per lane: f(W, L) as
+// compile-time constants for a class width known at run time (device: which body; host: which kernel).  What the callee
+// needs besides is handed through as arguments `a`: in k_apply_fused a capturing lambda compiles to other code than the
+// spelled-out dispatch did (tools/isa_digest.py), a lambda without captures to the same.
+template <class F, class... A>
+__host__ __device__ __forceinline__ void with_tile_width(int width, F &&f, const A &...a) {
+    if (width == 8) f(std::integral_constant<int, 8>{}, std::integral_constant<int, 1>{}, a...);
+    else if (width == 16) f(std::integral_constant<int, 16>{}, std::integral_constant<int, 1>{}, a...);
+    else f(std::integral_constant<int, 32>{}, std::integral_constant<int, 2>{}, a...);
+}
+
 template <int W, int L>
 __global__ __launch_bounds__(kBlock) void k_rows_tile(TileArgs p) {
     tiles_body<W, L>(p, blockIdx.x);
@@ -1163,11 +1163,25 @@ __device__ __forceinline__ void sweep_fetch(const u4 &cur, int &packed, int &val
     valbits = bcast16<Q>((int)(HALF ? cur.w : cur.y));
 }
 
-template <int DEPTH>
-// The register budget stays at 64 although the 158 KiB of accumulators allow only two wavefronts per SIMD: with 128 the
-// compiler keeps a full eight gathers in flight instead of seven, the wavefronts of a band drift apart and the L2 hit rate
-// falls from 53 to 41 % (item step 282 vs 266 us, profiles/r03j_*) -- the same effect as the continuous pipeline of section 8.
-__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(1, 8))) void k_sweep(SweepArgs p) {
+// f(0), f(1), ..., f(N - 1) with the argument a compile-time constant: the DPP lane of a step is an immediate
+template <class F, int... S>
+__device__ __forceinline__ void each_step(std::integer_sequence<int, S...>, F &&f) {
+    (f(std::integral_constant<int, S>{}), ...);
+}
+
+// The band sweep for tables of 68..96 columns (D = 80, 90), WIDE: a table row takes two DPP rows (lanes 0-15 columns 0..63,
+// lanes 16-31 the rest), a wavefront gathers two rows per instruction, a step has two entries, a slab is 512 bytes
+// (both DPP rows of a pair load the same 16 pieces), and an accumulator is 96 floats: 51 per wavefront, five rounds.
+constexpr int kWideRow = 96;   // floats per LDS accumulator row
+
+// Both sweeps.  What WIDE changes: the lane-to-column map, the LDS row width (64 / 96), the lanes without a column of the
+// table (lane_on) or without a slice of the accumulator row (lds_on), the slab size and the stride of the write-out.
+// p by value: taken by reference, the prologues of both kernels come out in another order than before the two were merged
+// (tools/isa_digest.py); like this they are the same code.
+template <int DEPTH, bool WIDE>
+__device__ __forceinline__ void sweep_body(const SweepArgs p) {
+    constexpr int kRow = WIDE ? kWideRow : 64;   // floats per LDS accumulator row
+    constexpr int kGroups = WIDE ? 2 : 4;        // table rows per gather instruction = entries of a step
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int lane = threadIdx.x & (kWave - 1);
     const int wib = threadIdx.x / kWave;
@@ -1175,76 +1189,95 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(1, 8))) 
     if (w >= p.n_waves) return;
     const int npieces = p.wave_npieces[w];
     if (npieces == 0) return;  // wave-uniform
-    const int l = lane & 15, g = lane >> 4;
-    const int c0 = min(l * 4, p.dim - 4);
-    float *acc = lds + (size_t)wib * (p.row_cap + 1) * 64;     // rows of 64 floats, row `row_cap` = dummy
-    {   // zero my region: (row_cap + 1) * 256 B, 1 KiB per wave-instruction
+    // lane group g (WIDE: pair of DPP rows; half = which DPP row of the pair) and the lane's first column c0
+    const int l = lane & 15, g = WIDE ? lane >> 5 : lane >> 4, half = WIDE ? (lane >> 4) & 1 : 0;
+    const int rest = p.dim - 64;                                          // WIDE: 4 .. 32 columns in the second DPP row
+    const bool lane_on = !WIDE || half == 0 || l * 4 < rest;              // lanes that own columns of the table
+    const bool lds_on = !WIDE || half == 0 || l < (kWideRow - 64) / 4;    // lanes that own a slice of the accumulator row
+    const int c0 = !WIDE ? min(l * 4, p.dim - 4) : half == 0 ? l * 4 : 64 + min(l * 4, rest - 4);
+    float *acc = lds + (size_t)wib * (p.row_cap + 1) * kRow;              // row `row_cap` = dummy
+    {   // zero my region: (row_cap + 1) * kRow * 4 B, 1 KiB per wave-instruction
         const f4 z = {0.0f, 0.0f, 0.0f, 0.0f};
-        for (int i = lane; i < (p.row_cap + 1) * 16; i += kWave) *reinterpret_cast<f4 *>(acc + i * 4) = z;
+        for (int i = lane; i < (p.row_cap + 1) * (kRow / 4); i += kWave) *reinterpret_cast<f4 *>(acc + i * 4) = z;
     }
     const auto xsrc = __builtin_amdgcn_make_buffer_rsrc((void *)p.x, 0, p.x_bytes, 0x00020000);
     const unsigned xs = (unsigned)p.x_stride * 4u, xoff = (unsigned)c0 * 4u;
-    float *mine = acc + l * 4;                                  // + piece * 64
+    float *mine = acc + half * 64 + (lds_on ? l * 4 : 0);                // + piece * kRow
     int slab = p.wave_slab_ptr[w];
     const int slab_end = p.wave_slab_ptr[w + 1];
     if (slab >= slab_end) return;
     PieceSlots piece_slots;
     piece_slots.load(p.piece_slot + (int64_t)w * p.row_cap, npieces, lane);
-    u4 nxt = __builtin_nontemporal_load(p.slabs + (int64_t)slab * kWave + lane);
+    // a slab = 32 steps of kGroups entries = kSlab pieces: 1 KiB, one piece per lane; WIDE 512 bytes, the lanes of pair g
+    // read pieces 16 g + l (both of its DPP rows the same ones)
+    constexpr int kSlab = 16 * kGroups;
+    const int piece_lane = WIDE ? g * 16 + l : lane;
+    u4 nxt = __builtin_nontemporal_load(p.slabs + (int64_t)slab * kSlab + piece_lane);
 #ifdef LGC_SWEEP_TRACE
     int tk = 0;
-    if (p.trace && lane == 0) p.trace[(int64_t)w * 16 + tk++] = __builtin_amdgcn_s_memrealtime();
+    if (!WIDE && p.trace && lane == 0) p.trace[(int64_t)w * 16 + tk++] = __builtin_amdgcn_s_memrealtime();
 #endif
     for (; slab < slab_end; ++slab) {
         const u4 cur = nxt;
-        if (slab + 1 < slab_end) nxt = __builtin_nontemporal_load(p.slabs + (int64_t)(slab + 1) * kWave + lane);
+        if (slab + 1 < slab_end) nxt = __builtin_nontemporal_load(p.slabs + (int64_t)(slab + 1) * kSlab + piece_lane);
         // 32 steps, DEPTH gathers in flight: issue step s + DEPTH after consuming step s
         f4 xv[DEPTH];
         int pk[DEPTH], vb[DEPTH];
-#define LGC_ISSUE(S)                                                                                                   \
-    {                                                                                                                  \
-        sweep_fetch<((S) >> 1), ((S) & 1)>(cur, pk[(S) % DEPTH], vb[(S) % DEPTH]);                                     \
-        xv[(S) % DEPTH] = __builtin_bit_cast(f4, __builtin_amdgcn_raw_buffer_load_b128(                                \
-            xsrc, __umul24(pk[(S) % DEPTH] & 0xFFFFFF, xs) + xoff, 0, 0));                          \
-    }
-#define LGC_CONSUME(S)                                                                                                 \
-    {                                                                                                                  \
-        float *row = mine + ((unsigned)pk[(S) % DEPTH] >> 24) * 64;                                                    \
-        f4 a = *reinterpret_cast<f4 *>(row);                                                                           \
-        const float v = __int_as_float(vb[(S) % DEPTH]);                                                               \
-        const f2 v2 = {v, v};                                                                                          \
-        const f2 lo = {xv[(S) % DEPTH].x, xv[(S) % DEPTH].y}, hi = {xv[(S) % DEPTH].z, xv[(S) % DEPTH].w};             \
-        const f2 alo = f2{a.x, a.y} + lo * v2, ahi = f2{a.z, a.w} + hi * v2;                                           \
-        *reinterpret_cast<f4 *>(row) = f4{alo.x, alo.y, ahi.x, ahi.y};                                                 \
-    }
-#define LGC_STEP(S)                                                                                                    \
-    LGC_CONSUME(S)                                                                                                     \
-    if constexpr ((S) + DEPTH < 32) LGC_ISSUE((S) + DEPTH)
-        LGC_ISSUE(0) LGC_ISSUE(1) LGC_ISSUE(2) LGC_ISSUE(3)
-        if constexpr (DEPTH >= 8) { LGC_ISSUE(4) LGC_ISSUE(5) LGC_ISSUE(6) LGC_ISSUE(7) }
-        LGC_STEP(0) LGC_STEP(1) LGC_STEP(2) LGC_STEP(3) LGC_STEP(4) LGC_STEP(5) LGC_STEP(6) LGC_STEP(7)
-        LGC_STEP(8) LGC_STEP(9) LGC_STEP(10) LGC_STEP(11) LGC_STEP(12) LGC_STEP(13) LGC_STEP(14) LGC_STEP(15)
-        LGC_STEP(16) LGC_STEP(17) LGC_STEP(18) LGC_STEP(19) LGC_STEP(20) LGC_STEP(21) LGC_STEP(22) LGC_STEP(23)
-        LGC_STEP(24) LGC_STEP(25) LGC_STEP(26) LGC_STEP(27) LGC_STEP(28) LGC_STEP(29) LGC_STEP(30) LGC_STEP(31)
-#undef LGC_STEP
-#undef LGC_CONSUME
-#undef LGC_ISSUE
+        auto issue = [&](auto step) __attribute__((always_inline)) {
+            constexpr int S = decltype(step)::value;
+            sweep_fetch<(S >> 1), (S & 1)>(cur, pk[S % DEPTH], vb[S % DEPTH]);
+            const int col = lane_on ? (pk[S % DEPTH] & 0xFFFFFF) : 0xFFFFFF;
+            xv[S % DEPTH] = __builtin_bit_cast(f4, __builtin_amdgcn_raw_buffer_load_b128(xsrc, __umul24(col, xs) + xoff, 0, 0));
+        };
+        auto consume = [&](auto step) __attribute__((always_inline)) {
+            constexpr int S = decltype(step)::value;
+            if (lds_on) {
+                float *row = mine + ((unsigned)pk[S % DEPTH] >> 24) * kRow;
+                f4 a = *reinterpret_cast<f4 *>(row);
+                const float v = __int_as_float(vb[S % DEPTH]);
+                const f2 v2 = {v, v};
+                const f2 lo = {xv[S % DEPTH].x, xv[S % DEPTH].y}, hi = {xv[S % DEPTH].z, xv[S % DEPTH].w};
+                const f2 alo = f2{a.x, a.y} + lo * v2, ahi = f2{a.z, a.w} + hi * v2;
+                *reinterpret_cast<f4 *>(row) = f4{alo.x, alo.y, ahi.x, ahi.y};
+            }
+        };
+        each_step(std::make_integer_sequence<int, DEPTH>{}, issue);
+        each_step(std::make_integer_sequence<int, 32>{}, [&](auto step) __attribute__((always_inline)) {
+            constexpr int S = decltype(step)::value;
+            consume(step);
+            if constexpr (S + DEPTH < 32) issue(std::integral_constant<int, S + DEPTH>{});
+        });
 #ifdef LGC_SWEEP_TRACE
-        if (p.trace && lane == 0 && tk < 15) p.trace[(int64_t)w * 16 + tk++] = __builtin_amdgcn_s_memrealtime();
+        if (!WIDE && p.trace && lane == 0 && tk < 15) p.trace[(int64_t)w * 16 + tk++] = __builtin_amdgcn_s_memrealtime();
 #endif
     }
 #ifdef LGC_SWEEP_TRACE
-    if (p.trace && lane == 0) p.trace[(int64_t)w * 16 + 15] = __builtin_amdgcn_s_memrealtime();   // end of the last slab
+    if (!WIDE && p.trace && lane == 0) p.trace[(int64_t)w * 16 + 15] = __builtin_amdgcn_s_memrealtime();   // end of the last slab
 #endif
-    // write my pieces to their partial slots: lane group g takes pieces g, g + 4, ... (every lane runs the shuffles)
-    for (int pc0 = 0; pc0 < npieces; pc0 += 4) {
+    // write my pieces to their partial slots: lane group (WIDE: pair) g takes pieces g, g + kGroups, ... (every lane runs
+    // the shuffles)
+    for (int pc0 = 0; pc0 < npieces; pc0 += kGroups) {
         const int pc = pc0 + g;
         const int slot = piece_slots.at(min(pc, npieces - 1));
-        if (pc < npieces) {
-            const f4 a = *reinterpret_cast<const f4 *>(mine + pc * 64);
-            __builtin_nontemporal_store(a, reinterpret_cast<f4u *>(p.partials + (int64_t)slot * p.pstride + p.pcol + c0));
+        if (pc < npieces && lane_on) {
+            const f4 a = *reinterpret_cast<const f4 *>(mine + pc * kRow);
+            float *dst = WIDE ? p.partials + (int64_t)slot * p.dim + c0 : p.partials + (int64_t)slot * p.pstride + p.pcol + c0;
+            __builtin_nontemporal_store(a, reinterpret_cast<f4u *>(dst));
         }
     }
+}
+
+template <int DEPTH>
+// The register budget stays at 64 although the 158 KiB of accumulators allow only two wavefronts per SIMD: with 128 the
+// compiler keeps a full eight gathers in flight instead of seven, the wavefronts of a band drift apart and the L2 hit rate
+// falls from 53 to 41 % (item step 282 vs 266 us, profiles/r03j_*) -- the same effect as the continuous pipeline of section 8.
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(1, 8))) void k_sweep(SweepArgs p) {
+    sweep_body<DEPTH, false>(p);
+}
+
+template <int DEPTH>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(1, 8))) void k_sweep_wide(SweepArgs p) {
+    sweep_body<DEPTH, true>(p);
 }
 
 // One launch per operator half and hop: chunk workgroups first (long rows run longest), then the tile classes.
@@ -1271,19 +1304,13 @@ __global__ __launch_bounds__(kBlock) void k_apply_fused(FusedArgs f) {
     for (int c = 0; c < 3; ++c) {
         if (c >= f.n_classes) return;
         if (b < f.blocks[c]) {
-            if constexpr (MODE == 2) {
-                if (f.width[c] == 8) tiles_body_dpp_wide<8, 1>(f.t[c], b);
-                else if (f.width[c] == 16) tiles_body_dpp_wide<16, 1>(f.t[c], b);
-                else tiles_body_dpp_wide<32, 2>(f.t[c], b);
-            } else if constexpr (MODE == 1) {
-                if (f.width[c] == 8) tiles_body_dpp<8, 1>(f.t[c], b);
-                else if (f.width[c] == 16) tiles_body_dpp<16, 1>(f.t[c], b);
-                else tiles_body_dpp<32, 2>(f.t[c], b);
-            } else {
-                if (f.width[c] == 8) tiles_body<8, 1>(f.t[c], b);
-                else if (f.width[c] == 16) tiles_body<16, 1>(f.t[c], b);
-                else tiles_body<32, 2>(f.t[c], b);
-            }
+            with_tile_width(f.width[c], [](auto w, auto l, const TileArgs &t, const int64_t block)
+                                            __attribute__((always_inline)) {
+                constexpr int W = decltype(w)::value, L = decltype(l)::value;
+                if constexpr (MODE == 2) tiles_body_dpp_wide<W, L>(t, block);
+                else if constexpr (MODE == 1) tiles_body_dpp<W, L>(t, block);
+                else tiles_body<W, L>(t, block);
+            }, f.t[c], b);
             return;
         }
         b -= f.blocks[c];
@@ -1315,86 +1342,6 @@ __global__ void k_build_tiles(const int32_t *__restrict__ rowptr, const lgc_entr
     slab[i] = v;
 }
 
-
-// The band sweep for tables of 68..96 columns (D = 80, 90): a table row takes two DPP rows (lanes 0-15 columns 0..63,
-// lanes 16-31 the rest), a wavefront gathers two rows per instruction, a step has two entries, a slab is 512 bytes
-// (both DPP rows of a pair load the same 16 pieces), and an accumulator is 96 floats: 51 per wavefront, five rounds.
-constexpr int kWideRow = 96;   // floats per LDS accumulator row
-
-template <int DEPTH>
-__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(1, 8))) void k_sweep_wide(SweepArgs p) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    const int lane = threadIdx.x & (kWave - 1);
-    const int wib = threadIdx.x / kWave;
-    const int w = __builtin_amdgcn_readfirstlane((int)(p.wave_begin + blockIdx.x * (kBlock / kWave) + wib));
-    if (w >= p.n_waves) return;
-    const int npieces = p.wave_npieces[w];
-    if (npieces == 0) return;  // wave-uniform
-    const int l = lane & 15, pair = lane >> 5, half = (lane >> 4) & 1;
-    const int rest = p.dim - 64;                                  // 4 .. 32 columns in the second DPP row
-    const bool lane_on = half == 0 || l * 4 < rest;               // lanes that own columns of the table
-    const bool lds_on = half == 0 || l < (kWideRow - 64) / 4;     // lanes that own a slice of the accumulator row
-    const int c0 = half == 0 ? l * 4 : 64 + min(l * 4, rest - 4);
-    float *acc = lds + (size_t)wib * (p.row_cap + 1) * kWideRow;  // row `row_cap` = dummy
-    {
-        const f4 z = {0.0f, 0.0f, 0.0f, 0.0f};
-        for (int i = lane; i < (p.row_cap + 1) * (kWideRow / 4); i += kWave) *reinterpret_cast<f4 *>(acc + i * 4) = z;
-    }
-    const auto xsrc = __builtin_amdgcn_make_buffer_rsrc((void *)p.x, 0, p.x_bytes, 0x00020000);
-    const unsigned xs = (unsigned)p.x_stride * 4u, xoff = (unsigned)c0 * 4u;
-    float *mine = acc + half * 64 + (lds_on ? l * 4 : 0);        // + piece * kWideRow
-    int slab = p.wave_slab_ptr[w];
-    const int slab_end = p.wave_slab_ptr[w + 1];
-    if (slab >= slab_end) return;
-    PieceSlots piece_slots;
-    piece_slots.load(p.piece_slot + (int64_t)w * p.row_cap, npieces, lane);
-    // a 512-byte slab = 32 pieces; lanes of pair g read pieces 16 g + l (both of its DPP rows the same ones)
-    const int piece_lane = pair * 16 + l;
-    u4 nxt = __builtin_nontemporal_load(p.slabs + (int64_t)slab * 32 + piece_lane);
-    for (; slab < slab_end; ++slab) {
-        const u4 cur = nxt;
-        if (slab + 1 < slab_end) nxt = __builtin_nontemporal_load(p.slabs + (int64_t)(slab + 1) * 32 + piece_lane);
-        f4 xv[DEPTH];
-        int pk[DEPTH], vb[DEPTH];
-#define LGC_ISSUE(S)                                                                                                   \
-    {                                                                                                                  \
-        sweep_fetch<((S) >> 1), ((S) & 1)>(cur, pk[(S) % DEPTH], vb[(S) % DEPTH]);                                     \
-        const int col_ = lane_on ? (pk[(S) % DEPTH] & 0xFFFFFF) : 0xFFFFFF;                                            \
-        xv[(S) % DEPTH] = __builtin_bit_cast(f4, __builtin_amdgcn_raw_buffer_load_b128(                                \
-            xsrc, __umul24(col_, xs) + xoff, 0, 0));                                                \
-    }
-#define LGC_CONSUME(S)                                                                                                 \
-    if (lds_on) {                                                                                                      \
-        float *row = mine + ((unsigned)pk[(S) % DEPTH] >> 24) * kWideRow;                                              \
-        f4 a = *reinterpret_cast<f4 *>(row);                                                                           \
-        const float v = __int_as_float(vb[(S) % DEPTH]);                                                               \
-        const f2 v2 = {v, v};                                                                                          \
-        const f2 lo = {xv[(S) % DEPTH].x, xv[(S) % DEPTH].y}, hi = {xv[(S) % DEPTH].z, xv[(S) % DEPTH].w};             \
-        const f2 alo = f2{a.x, a.y} + lo * v2, ahi = f2{a.z, a.w} + hi * v2;                                           \
-        *reinterpret_cast<f4 *>(row) = f4{alo.x, alo.y, ahi.x, ahi.y};                                                 \
-    }
-#define LGC_STEP(S)                                                                                                    \
-    LGC_CONSUME(S)                                                                                                     \
-    if constexpr ((S) + DEPTH < 32) LGC_ISSUE((S) + DEPTH)
-        LGC_ISSUE(0) LGC_ISSUE(1) LGC_ISSUE(2) LGC_ISSUE(3) LGC_ISSUE(4) LGC_ISSUE(5) LGC_ISSUE(6) LGC_ISSUE(7)
-        LGC_STEP(0) LGC_STEP(1) LGC_STEP(2) LGC_STEP(3) LGC_STEP(4) LGC_STEP(5) LGC_STEP(6) LGC_STEP(7)
-        LGC_STEP(8) LGC_STEP(9) LGC_STEP(10) LGC_STEP(11) LGC_STEP(12) LGC_STEP(13) LGC_STEP(14) LGC_STEP(15)
-        LGC_STEP(16) LGC_STEP(17) LGC_STEP(18) LGC_STEP(19) LGC_STEP(20) LGC_STEP(21) LGC_STEP(22) LGC_STEP(23)
-        LGC_STEP(24) LGC_STEP(25) LGC_STEP(26) LGC_STEP(27) LGC_STEP(28) LGC_STEP(29) LGC_STEP(30) LGC_STEP(31)
-#undef LGC_STEP
-#undef LGC_CONSUME
-#undef LGC_ISSUE
-    }
-    // write my pieces to their partial slots: pair g takes pieces g, g + 2, ... (every lane runs the shuffles)
-    for (int pc0 = 0; pc0 < npieces; pc0 += 2) {
-        const int pc = pc0 + pair;
-        const int slot = piece_slots.at(min(pc, npieces - 1));
-        if (pc < npieces && lane_on) {
-            const f4 a = *reinterpret_cast<const f4 *>(mine + pc * kWideRow);
-            __builtin_nontemporal_store(a, reinterpret_cast<f4u *>(p.partials + (int64_t)slot * p.dim + c0));
-        }
-    }
-}
 
 // Sum of a swept row's partial slots + epilogue, one launch:
 //   blocks [0, n_wide)   rows cut into many pieces (hubs): one WORKGROUP per row -- unit (wave, lane group) u of 16
@@ -1484,37 +1431,6 @@ __global__ __launch_bounds__(kBlock) void k_sweep_combine(SpmmArgs p, const lgc_
             for (int i = 0; i < VEC; ++i) acc.v[i] = __fadd_rn(acc.v[i], t[j].v[i]);
     }
     finish_row<VEC, SpmmArgs>(p, mr.row, c0, acc, rv);
-}
-
-// Fixed-order sum of runs: `key` is sorted; position t is a HEAD when key[t] != key[t - 1].  The lane group of a head adds
-// vals[t], vals[t + 1], ... of its run in that order (fp32, sequential) and writes y[dest[t]] = (accumulate ? y[dest[t]]
-// : 0) + scale * sum; positions that are not heads, and heads with dest < 0, write nothing.  Every destination row is
-// owned by one lane group: no atomics, the same bits on every run -- the gradient of a scoring step has a few thousand
-// non-zero rows (src/lightgcn.py:123-125 scores 2B pairs), repeated nodes are summed here instead of by float atomics.
-__global__ __launch_bounds__(kBlock) void k_segment_sum(const int64_t *__restrict__ key, const int64_t *__restrict__ dest,
-                                                       const float *__restrict__ vals, const int32_t *__restrict__ vals_index,
-                                                       int64_t n, float scale,
-                                                       float *__restrict__ y, int64_t y_stride, int64_t y_rows, int32_t dim,
-                                                       int32_t accumulate) {
-    const int lane = threadIdx.x & (kWave - 1);
-    const int lpr = (dim + 3) / 4, groups = kWave / lpr;
-    const int g = lane / lpr, l = lane - g * lpr;
-    const int64_t t = ((int64_t)blockIdx.x * (kBlock / kWave) + (threadIdx.x / kWave)) * groups + g;
-    if (g >= groups || t >= n) return;
-    const int64_t k = key[t];
-    if (t > 0 && key[t - 1] == k) return;
-    const int64_t d = dest[t];
-    if (d < 0 || d >= y_rows) return;
-    const int c0 = l * 4;
-    float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-    for (int64_t u = t; u < n && key[u] == k; ++u) {
-        const int64_t v = vals_index ? (int64_t)vals_index[u] : u;   // the sorted position's row of an UNSORTED value table
-        for (int i = 0; i < 4; ++i)
-            if (c0 + i < dim) acc[i] = __fadd_rn(acc[i], vals[v * dim + c0 + i]);
-    }
-    float *out = y + d * y_stride + c0;
-    for (int i = 0; i < 4; ++i)
-        if (c0 + i < dim) out[i] = __fadd_rn(accumulate ? out[i] : 0.0f, __fmul_rn(scale, acc[i]));
 }
 
 // The columns of the listed rows get `value` in `mark` (lgc_seed_mark): the rows the seeded pull has to look at.  Every
@@ -1674,237 +1590,6 @@ __global__ void k_tile_pack(const int32_t *__restrict__ rowptr, const int32_t *_
     meta[t] = m;
 }
 
-// ----------------------------------------------------------------------------------------
-// Seed preparation of the sparse backward pass (lgc_seed_prepare): ONE workgroup sorts up to kSeedMax row ids and
-// derives everything the segment sums and the seeded pull need -- what the host code did with ~25 small launches
-// (sort, gathers, compares, index_puts) per training step.
-// ----------------------------------------------------------------------------------------
-constexpr int kSeedMax = 8192;
-constexpr int kSeedBlock = 1024;
-
-// Pass 1 (m / 8 workgroups): every workgroup keeps all m keys -- row + 1, ids outside the table as "no row" = 0; the
-// position is the tie-break -- in LDS and RANKS eight of them by counting the smaller ones, 32 threads per key, each
-// scanning 1/32 of the array (LDS reads: a wavefront reads two addresses, both broadcasts); (key, position) pairs are
-// distinct, so the ranks are a permutation and sorted[rank] = key is a stable sort by row.  The scan is a dependent chain of
-// LDS reads, so its time falls with the threads per key: 4 -> 36.7 us, 8 -> 19.5 us at m = 4096.  A one-workgroup bitonic sort of
-// the same keys took 38-51 us (78 barrier stages of LDS-bound 64-bit compare-exchanges); 1024 keys per workgroup with
-// one thread per key 69 us (four workgroups on the whole chip).
-constexpr int kRankKeys = 8;      // keys ranked per workgroup of 256 threads: 32 threads per key (19.5 us with 8, 36.7 with 4)
-
-__global__ __launch_bounds__(kBlock) void k_seed_rank(const int64_t *__restrict__ rows, int32_t m, int64_t n_nodes,
-                                                     unsigned long long *__restrict__ sorted) {
-    __shared__ __attribute__((aligned(16))) uint32_t key[kSeedMax];   // row + 1 (0 = "no row"); position = array index: 32 KiB
-    __shared__ int part[kBlock];
-    for (int i = threadIdx.x; i < m; i += kBlock) {
-        int64_t r = rows[i];
-        if (r < 0 || r >= n_nodes) r = -1;
-        key[i] = (uint32_t)(r + 1);
-    }
-    __syncthreads();
-    constexpr int kParts = kBlock / kRankKeys;
-    const int k = threadIdx.x & (kRankKeys - 1), q = threadIdx.x / kRankKeys;     // key k of this workgroup, slice q of the array
-    const int i = blockIdx.x * kRankKeys + k;
-    const uint32_t mine = i < m ? key[i] : 0u;
-    const int per = ((m + 4 * kParts - 1) / (4 * kParts)) * 4, lo = min(m, q * per), hi = min(m, lo + per);   // whole uint4s
-    // (row, position) order: everything with a smaller row, and the equal rows in front of me; branch-free, four keys per
-    // LDS read, two reads in flight
-    int rank = 0;
-    int j = lo;
-    auto count4 = [&](const u4 o, int at) {
-        return (int)(o.x < mine) + (int)((o.x == mine) & (at < i)) + (int)(o.y < mine) + (int)((o.y == mine) & (at + 1 < i)) +
-               (int)(o.z < mine) + (int)((o.z == mine) & (at + 2 < i)) + (int)(o.w < mine) + (int)((o.w == mine) & (at + 3 < i));
-    };
-    for (; j + 8 <= hi; j += 8) {
-        const u4 o0 = *reinterpret_cast<const u4 *>(key + j), o1 = *reinterpret_cast<const u4 *>(key + j + 4);
-        rank += count4(o0, j) + count4(o1, j + 4);
-    }
-    for (; j < hi; ++j) {
-        const uint32_t o = key[j];
-        rank += (int)(o < mine) + (int)((o == mine) & (j < i));
-    }
-    part[threadIdx.x] = rank;
-    __syncthreads();
-    if (q == 0 && i < m) {
-        int total = 0;
-#pragma unroll
-        for (int p = 0; p < kParts; ++p) total += part[p * kRankKeys + k];
-        sorted[total] = ((unsigned long long)mine << 13) | (unsigned)i;
-    }
-}
-
-// Pass 2: one thread per sorted position -- run heads, destination lists, the pull's column map.
-__global__ void k_seed_finish(const unsigned long long *__restrict__ key, int32_t m, int64_t split,
-                              int64_t *__restrict__ rows_sorted, int32_t *__restrict__ perm, int64_t *__restrict__ dest_item,
-                              int64_t *__restrict__ dest_slot, int64_t *__restrict__ dest_user,
-                              uint8_t *__restrict__ col_flag, int32_t *__restrict__ col_slot) {
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= m) return;
-    const unsigned long long k = key[t];
-    const int64_t row = (int64_t)(k >> 13) - 1;
-    const bool head = t == 0 || (int64_t)(key[t - 1] >> 13) - 1 != row;
-    const bool user = row >= 0 && row < split, item = row >= split;
-    rows_sorted[t] = row;
-    perm[t] = (int32_t)(k & 0x1FFF);
-    dest_item[t] = (head && item) ? row : -1;
-    dest_slot[t] = (head && user) ? t : -1;
-    dest_user[t] = (head && user) ? row : -1;
-    if (head && user && col_flag) {
-        col_flag[row] = 1;
-        col_slot[row] = t;
-    }
-}
-
-// flag[row] = value for the user rows (0 <= row < split) of a sorted row list: takes the flags of a step's seeds back
-__global__ void k_seed_flags(const int64_t *__restrict__ rows_sorted, int64_t m, int64_t split, uint8_t *__restrict__ flag,
-                             uint8_t value) {
-    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= m) return;
-    const int64_t row = rows_sorted[t];
-    if (row >= 0 && row < split) flag[row] = value;
-}
-
-// Pair scoring that keeps what the backward pass needs (lgc_pair_dot_rows): scores as k_pair_dot, plus the two gathered
-// rows of every pair and a validity byte -- instead of four compares, three ands, two clamps and two row gathers on the
-// host side.  An out-of-range pair scores NaN, keeps zero rows, ok = 0, and raises the status bit.
-__global__ __launch_bounds__(kBlock) void k_pair_dot_rows(const float *__restrict__ emb, int64_t stride, int32_t dim,
-                                                         int64_t n_nodes, const int64_t *__restrict__ idx0,
-                                                         const int64_t *__restrict__ idx1, int64_t n_pairs,
-                                                         float *__restrict__ scores, float *__restrict__ rows0,
-                                                         float *__restrict__ rows1, uint8_t *__restrict__ ok,
-                                                         int32_t *__restrict__ status) {
-    const int lane = threadIdx.x & (kWave - 1);
-    const int64_t m = (int64_t)blockIdx.x * (kBlock / kWave) + (threadIdx.x / kWave);
-    if (m >= n_pairs) return;
-    const int64_t a = idx0[m], b = idx1[m];
-    const bool valid = a >= 0 && a < n_nodes && b >= 0 && b < n_nodes;   // wave-uniform
-    if (!valid && lane == 0) {
-        atomicOr(status, LGC_ST_INDEX_OOB);
-        scores[m] = NAN;
-    }
-    if (lane == 0 && ok) ok[m] = valid ? 1 : 0;
-    const float *pa = emb + a * stride, *pb = emb + b * stride;
-    float s = 0.0f;
-    for (int c = lane; c < dim; c += kWave) {
-        const float va = valid ? pa[c] : 0.0f, vb = valid ? pb[c] : 0.0f;
-        s += va * vb;
-        if (rows0) rows0[m * dim + c] = va;
-        if (rows1) rows1[m * dim + c] = vb;
-    }
-    if (!valid) return;
-#pragma unroll
-    for (int off = kWave / 2; off > 0; off >>= 1) s += __shfl_xor(s, off);
-    if (lane == 0) scores[m] = s;
-}
-
-// The seed of the backward pass from the gradient of the scores (lgc_pair_seed_vals):
-//   vals[m]           = g[m] * rows1[m]      d score_m / d out[idx0[m]] = out[idx1[m]]
-//   vals[n_pairs + m] = g[m] * rows0[m]      d score_m / d out[idx1[m]] = out[idx0[m]]
-// with g[m] = mask[m] ? grad_scores[m] * (*grad_scale) : 0.  grad_scale: an optional DEVICE scalar (the upstream
-// gradient of a loss this node computed itself), so that no host sync is needed to read it.
-__global__ __launch_bounds__(kBlock) void k_pair_seed_vals(const float *__restrict__ grad_scores, const uint8_t *__restrict__ mask,
-                                                          const float *__restrict__ grad_scale, const float *__restrict__ rows0,
-                                                          const float *__restrict__ rows1, int64_t n_pairs, int32_t dim,
-                                                          float *__restrict__ vals) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_pairs * dim) return;
-    const int64_t m = i / dim;
-    float g = (mask == nullptr || mask[m]) ? grad_scores[m] : 0.0f;
-    if (grad_scale) g = __fmul_rn(g, *grad_scale);
-    vals[i] = __fmul_rn(g, rows1[i]);
-    vals[n_pairs * dim + i] = __fmul_rn(g, rows0[i]);
-}
-
-// BPR loss of one batch of triples and its gradient with respect to the scores (lgc_bpr_loss): what
-// `recommendation_loss(out[:B], out[B:], 0) * B` of src/train_lightgcn.py:141 (src/lightgcn.py:262-286 with lambda_reg = 0)
-// and its autograd compute with ~15 launches:  loss = -sum_{t: mask[t]} log sigmoid(s[t] - s[B + t]) / size,
-// grad[t] = -sigmoid(-(s[t] - s[B + t])) / size, grad[B + t] = -grad[t] (0 where the mask is off).  One workgroup, a fixed
-// reduction tree: the same bits on every run.  logsigmoid(d) = min(d, 0) - log1p(exp(-|d|)), torch's formula.
-__global__ __launch_bounds__(kSeedBlock) void k_bpr_loss(const float *__restrict__ scores, const uint8_t *__restrict__ mask,
-                                                        int64_t n_triples, float inv_size, float *__restrict__ loss,
-                                                        float *__restrict__ grad) {
-    __shared__ float part[kSeedBlock];
-    float acc = 0.0f;
-    for (int64_t t = threadIdx.x; t < n_triples; t += kSeedBlock) {
-        const bool on = mask == nullptr || mask[t] != 0;
-        const float d = on ? scores[t] - scores[n_triples + t] : 0.0f;
-        const float ls = fminf(d, 0.0f) - log1pf(expf(-fabsf(d)));
-        const float sg = 1.0f / (1.0f + expf(d));                  // sigmoid(-d)
-        if (on) acc += ls;
-        grad[t] = on ? -sg * inv_size : 0.0f;
-        grad[n_triples + t] = on ? sg * inv_size : 0.0f;
-    }
-    part[threadIdx.x] = acc;
-    __syncthreads();
-    for (int s = kSeedBlock / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) part[threadIdx.x] += part[threadIdx.x + s];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) loss[0] = -part[0] * inv_size;
-}
-
-// The regulariser of src/utils_v2.py:193-211 on three id lists of one table (lgc_reg_rows): what
-//   (1/2) * (w[u].norm().pow(2) + w[p].norm().pow(2) + w[n].norm().pow(2)) / size * decay
-// costs as 13 torch launches (three gathers into [B, D] copies, three norms, pows, adds, scalings) plus nine more that
-// normalise the ids for the gradient's row list -- in ONE workgroup: a thread per row (columns in order), per-list sums of
-// squares added up in a fixed order (the same bits on every run),
-// value = scale * ((sqrt S_u)^2 + (sqrt S_p)^2 + (sqrt S_n)^2) like the expression above.  rows_out (int64 [m0 + m1 + m2],
-// optional): the ids as row numbers, negative ids wrapped (torch's indexing), an id outside [-n_rows, n_rows) as -1 = "no
-// row" -- such an id contributes nothing and sets LGC_ST_INDEX_OOB (upstream's gather raises).
-__global__ __launch_bounds__(kSeedBlock) void k_reg_rows(const float *__restrict__ w, int64_t stride, int32_t dim, int64_t n_rows,
-                                                        const int64_t *__restrict__ ids0, int64_t m0,
-                                                        const int64_t *__restrict__ ids1, int64_t m1,
-                                                        const int64_t *__restrict__ ids2, int64_t m2, float scale,
-                                                        float *__restrict__ value, int64_t *__restrict__ rows_out,
-                                                        int32_t *__restrict__ status) {
-    constexpr int kWaves = kSeedBlock / kWave;
-    __shared__ float part[3][kWaves];
-    const int lane = threadIdx.x & (kWave - 1), wv = threadIdx.x / kWave;
-    const int64_t total = m0 + m1 + m2;
-    float acc[3] = {0.0f, 0.0f, 0.0f};
-    // a THREAD per row (a wavefront per row made one workgroup walk 3 B rows through two dependent loads each: 200 us): the
-    // dim / 4 loads of a row are independent, a thread has all of them in flight
-    for (int64_t t = threadIdx.x; t < total; t += kSeedBlock) {
-        const int which = t < m0 ? 0 : (t < m0 + m1 ? 1 : 2);
-        int64_t id = which == 0 ? ids0[t] : (which == 1 ? ids1[t - m0] : ids2[t - m0 - m1]);
-        if (id < 0) id += n_rows;
-        const bool ok = id >= 0 && id < n_rows;
-        if (rows_out != nullptr) rows_out[t] = ok ? id : -1;
-        if (!ok) {
-            atomicOr(status, LGC_ST_INDEX_OOB);
-            continue;
-        }
-        const float *row = w + id * stride;
-        float sq = 0.0f;
-        int c = 0;
-        for (; c + 4 <= dim; c += 4) {
-            const f4 v = *reinterpret_cast<const f4u *>(row + c);
-            sq += v.x * v.x;
-            sq += v.y * v.y;
-            sq += v.z * v.z;
-            sq += v.w * v.w;
-        }
-        for (; c < dim; ++c) sq += row[c] * row[c];
-        acc[which] += sq;
-    }
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        float v = acc[j];
-        for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_down(v, off);
-        if (lane == 0) part[j][wv] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float out = 0.0f;
-        for (int j = 0; j < 3; ++j) {
-            float sum = 0.0f;
-            for (int i = 0; i < kWaves; ++i) sum += part[j][i];
-            const float nrm = sqrtf(sum);
-            out += nrm * nrm;
-        }
-        value[0] = out * scale;
-    }
-}
-
 struct LincombArgs {
     const float *src[LGC_MAX_TERMS];
     int64_t stride[LGC_MAX_TERMS];
@@ -1922,425 +1607,6 @@ __global__ void k_lincomb(float *__restrict__ y, int64_t y_stride, LincombArgs a
         for (int t = 1; t < a.n_terms; ++t) v = __fadd_rn(v, __fmul_rn(a.coef[t], a.src[t][row * a.stride[t] + c]));
         y[row * y_stride + c] = v;
     }
-}
-
-// ----------------------------------------------------------------------------------------
-// Dense Adam step over the embedding table (the caller's optimizer.step(), src/train_lightgcn.py:58,147)
-// ----------------------------------------------------------------------------------------
-// One pass: w, g, m, v read once, w, m, v written once (7 x 434 MB at 1.7 M x 64): torch.optim.Adam's arithmetic for
-// amsgrad=False, weight_decay=0, maximize=False --
-//   m <- m + (g - m) (1 - beta1);  v <- beta2 v + (1 - beta2) g g;  w <- w - (lr / bc1) m / (sqrt(v) / sqrt(bc2) + eps)
-// with bc1 = 1 - beta1^t, bc2 = 1 - beta2^t computed by the host in double and handed over as step_size, bc2_sqrt.
-// (1 - beta1) and (1 - beta2) come from the host, rounded from double like torch's scalars: 1.0f - 0.999f is 4.7e-5 off.
-constexpr int kAdamU = 2;
-__global__ __launch_bounds__(kBlock) void k_adam(float *__restrict__ w, const float *__restrict__ g, float *__restrict__ m,
-                                                float *__restrict__ v, int64_t n4, int64_t n, float beta2, float omb1, float omb2,
-                                                float eps, float step_size, float bc2_sqrt, const float *__restrict__ hyper) {
-    if (hyper != nullptr) {   // lgc_adam_step_hp: the step's scalars live in device memory (a captured launch is replayed with
-        omb1 = hyper[0]; beta2 = hyper[1]; omb2 = hyper[2]; eps = hyper[3]; step_size = hyper[4]; bc2_sqrt = hyper[5];   // new values)
-    }
-    auto one = [&](float &wi, float gi, float &mi, float &vi) {
-        mi = mi + (gi - mi) * omb1;
-        vi = beta2 * vi + omb2 * gi * gi;
-        wi = wi - step_size * (mi / (sqrtf(vi) / bc2_sqrt + eps));
-    };
-    constexpr int U = kAdamU;                 // float4s per thread and array: 8 loads in flight per thread (1 / 4: the same time)
-    const int64_t base = ((int64_t)blockIdx.x * blockDim.x) * U + threadIdx.x;
-    f4 w4[U], g4[U], m4[U], v4[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-        const int64_t i = base + (int64_t)u * blockDim.x;
-        if (i < n4) {
-            w4[u] = reinterpret_cast<f4 *>(w)[i];
-            g4[u] = __builtin_nontemporal_load(reinterpret_cast<const f4 *>(g) + i);   // read once: 566 -> 546 us for 108 M elements
-            m4[u] = reinterpret_cast<f4 *>(m)[i];
-            v4[u] = reinterpret_cast<f4 *>(v)[i];
-        }
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-        const int64_t i = base + (int64_t)u * blockDim.x;
-        if (i < n4) {
-            float wv[4] = {w4[u].x, w4[u].y, w4[u].z, w4[u].w}, gv[4] = {g4[u].x, g4[u].y, g4[u].z, g4[u].w};
-            float mv[4] = {m4[u].x, m4[u].y, m4[u].z, m4[u].w}, vv[4] = {v4[u].x, v4[u].y, v4[u].z, v4[u].w};
-#pragma unroll
-            for (int j = 0; j < 4; ++j) one(wv[j], gv[j], mv[j], vv[j]);
-            reinterpret_cast<f4 *>(w)[i] = f4{wv[0], wv[1], wv[2], wv[3]};
-            reinterpret_cast<f4 *>(m)[i] = f4{mv[0], mv[1], mv[2], mv[3]};
-            reinterpret_cast<f4 *>(v)[i] = f4{vv[0], vv[1], vv[2], vv[3]};
-        }
-    }
-    // tail (n not a multiple of 4): the first threads of block 0
-    const int64_t t = n4 * 4 + threadIdx.x;
-    if (blockIdx.x == 0 && t < n) one(w[t], g[t], m[t], v[t]);
-}
-
-// ----------------------------------------------------------------------------------------
-// Pair scoring
-// ----------------------------------------------------------------------------------------
-// One wavefront per pair; lanes stride the feature axis, butterfly reduce over 64 lanes.
-__global__ __launch_bounds__(kBlock) void k_pair_dot(const float *__restrict__ emb, int64_t stride, int32_t dim,
-                                                    int64_t n_nodes, const int64_t *__restrict__ idx0,
-                                                    const int64_t *__restrict__ idx1, int64_t n_pairs,
-                                                    float *__restrict__ scores, int32_t *__restrict__ status) {
-    const int lane = threadIdx.x & (kWave - 1);
-    const int64_t m = (int64_t)blockIdx.x * (kBlock / kWave) + (threadIdx.x / kWave);
-    if (m >= n_pairs) return;
-    const int64_t a = idx0[m], b = idx1[m];
-    if (a < 0 || a >= n_nodes || b < 0 || b >= n_nodes) {  // wave-uniform
-        if (lane == 0) {
-            atomicOr(status, LGC_ST_INDEX_OOB);
-            scores[m] = NAN;
-        }
-        return;
-    }
-    const float *pa = emb + a * stride, *pb = emb + b * stride;
-    float s = 0.0f;
-    for (int c = lane; c < dim; c += kWave) s += pa[c] * pb[c];
-#pragma unroll
-    for (int off = kWave / 2; off > 0; off >>= 1) s += __shfl_xor(s, off);
-    if (lane == 0) scores[m] = s;
-}
-
-// ----------------------------------------------------------------------------------------
-// Serving tail: multiplicative seen-mask + top-k per row, on the device
-// ----------------------------------------------------------------------------------------
-// masked[i] = score[i] * (1 - seen[i])  (src/lightgcn.py:175 -- seen items become 0, they are not removed), then the
-// k largest by (value descending, index ascending).  One workgroup per row.  Rows of up to 65,536 columns are read
-// ONCE: each thread keeps its 64 order-preserving keys in registers.  Short cut: the k-th largest of the 1,024
-// per-thread maxima bounds the k-th largest element from below; the few elements in or above its 11-bit bin go to a
-// list in LDS and each counts the entries ahead of it (= its output position).  Heavily tied or flat rows (list
-// longer than 512) and wider rows take the general path: three radix passes (11 + 11 + 10 bits, histograms in LDS)
-// find the k-th largest key T, one pass collects everything above T plus as many elements equal to T as are still
-// needed -- lowest indices first -- and a bitonic sort orders the k winners.  Nothing but [rows, k] leaves the device.
-constexpr int kTopkMax = 256;
-constexpr int kTopkBlock = 1024;   // 16 wavefronts on one row: a single-row request is latency-bound on one CU
-
-__device__ __forceinline__ uint32_t order_key(float v) {
-    const uint32_t u = __float_as_uint(__fadd_rn(v, 0.0f));   // -0 -> +0: they compare equal (a seen item's 0 * score)
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);        // ascending with the value; +NaN above +inf like torch.topk
-}
-
-constexpr int kTopkRegs = 64;      // keys a thread can hold: rows up to kTopkRegs * kTopkBlock columns are read once
-constexpr int kTopkCopies = 4;     // histogram copies (lane & 3), one bank apart: scores crowd into a few exponent bins
-constexpr int kTopkHistStride = 2049;
-constexpr int kTopkShort = 512;    // longest candidate list the short cut ranks by counting
-
-// REGS: the row's masked keys live in registers (one read of the row, all passes on registers); otherwise every pass
-// streams the row again (rows wider than kTopkRegs * kTopkBlock columns).
-#ifdef LGC_TOPK_TRACE   // debug builds (tools/topk_trace.py): phase time stamps of block 0
-__device__ unsigned long long g_topk_trace[16];
-#define LGC_TOPK_STAMP(slot) do { if (blockIdx.x == 0 && threadIdx.x == 0) g_topk_trace[slot] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#else
-#define LGC_TOPK_STAMP(slot) do { } while (0)
-#endif
-
-// MASK: 0 none, 1 dense [rows, n_cols] floats, 2 per-user item lists.
-template <bool REGS, int MASK>
-__global__ __launch_bounds__(kTopkBlock) void k_mask_topk(const float *__restrict__ scores, int64_t score_stride,
-                                                         const float *__restrict__ seen, int64_t seen_stride,
-                                                         const int64_t *__restrict__ list_ptr,
-                                                         const int64_t *__restrict__ list_items,
-                                                         const int64_t *__restrict__ list_rows, int32_t n_cols,
-                                                         int32_t k, int64_t *__restrict__ out_index,
-                                                         float *__restrict__ out_value) {
-    extern __shared__ uint32_t seen_bits[];     // list form of the mask: one bit per column, built here
-    __shared__ uint32_t hist[kTopkCopies * kTopkHistStride];
-    __shared__ uint32_t cand_key[kTopkMax], cand_inv[kTopkMax];   // candidates: key, then ~index (lowest index wins ties)
-    __shared__ uint32_t sh_bin, sh_need, sh_count, sh_short, sh_wave[kTopkBlock / kWave];
-    const int tid = threadIdx.x, lane = tid & (kWave - 1), wv = tid / kWave;
-    const float *srow = scores + (int64_t)blockIdx.x * score_stride;
-    const float *mrow = MASK == 1 ? seen + (int64_t)blockIdx.x * seen_stride : nullptr;
-    LGC_TOPK_STAMP(0);
-    if (MASK == 2) {   // seen items of this row's user as a bitmask in LDS: the dense [rows, n_cols] mask never exists
-        for (int b = tid; b < (n_cols + 31) / 32; b += kTopkBlock) seen_bits[b] = 0u;
-        __syncthreads();
-        const int64_t u = list_rows ? list_rows[blockIdx.x] : (int64_t)blockIdx.x;
-        for (int64_t e = list_ptr[u] + tid; e < list_ptr[u + 1]; e += kTopkBlock) {
-            const int64_t it = list_items[e];
-            if (it >= 0 && it < n_cols) atomicOr(&seen_bits[it >> 5], 1u << (it & 31));
-        }
-        __syncthreads();
-    }
-    // score * (1 - seen) in upstream's arithmetic; the list form has seen = 1 for listed columns, 0 elsewhere
-    auto masked_at = [&](float s, float m, int i) {
-        if (MASK == 2) return (seen_bits[i >> 5] >> (i & 31)) & 1u ? __fmul_rn(s, 0.0f) : s;
-        return MASK == 1 ? __fmul_rn(s, __fsub_rn(1.0f, m)) : s;
-    };
-    // slots past the row end hold key 0, below every real key (real keys are lifted to >= 1: only the one -NaN
-    // pattern 0xFFFFFFFF moves, onto its neighbour), so the passes need no bounds test.  Loads are clamped, not
-    // predicated: no divergent control flow around them.
-    auto key_of = [&](float s, float m, int i) {
-        const uint32_t key = max(order_key(masked_at(s, m, min(i, n_cols - 1))), 1u);
-        return i < n_cols ? key : 0u;
-    };
-    uint32_t keys[REGS ? kTopkRegs : 1];
-    if (REGS) {
-        constexpr int G = 16;                         // independent loads per thread in flight: one CU, latency-bound
-#pragma unroll
-        for (int j0 = 0; j0 < kTopkRegs; j0 += G) {
-            if (j0 * kTopkBlock < n_cols) {           // block-uniform
-                float sv[G], mv[G];
-#pragma unroll
-                for (int j = 0; j < G; ++j) {
-                    const int i = min((j0 + j) * kTopkBlock + tid, n_cols - 1);
-                    sv[j] = srow[i];
-                    mv[j] = MASK == 1 ? mrow[i] : 0.0f;
-                }
-#pragma unroll
-                for (int j = 0; j < G; ++j) keys[j0 + j] = key_of(sv[j], mv[j], (j0 + j) * kTopkBlock + tid);
-            } else {
-#pragma unroll
-                for (int j = 0; j < G; ++j) keys[j0 + j] = 0u;
-            }
-        }
-    }
-    LGC_TOPK_STAMP(1);
-    uint32_t *my_hist = hist + (lane & (kTopkCopies - 1)) * kTopkHistStride;
-    // Walk the nb bins of hist[] down from the top until `want` elements are covered: sh_bin = the bin that crosses,
-    // sh_need = elements still wanted from it, sh_count = its population.  Thread t owns nb / 1024 bins (block scan).
-    auto find_bin = [&](int nb, uint32_t want) {
-        const int per = nb / kTopkBlock;                     // 2 or 1
-        uint32_t mine = 0;
-        for (int j = 0; j < per; ++j) mine += hist[nb - 1 - (tid * per + j)];
-        uint32_t incl = mine;                                // inclusive scan, thread 0 = highest bins
-        for (int off = 1; off < kWave; off <<= 1) {
-            const uint32_t o = __shfl_up(incl, off);
-            if (lane >= off) incl += o;
-        }
-        if (lane == kWave - 1) sh_wave[wv] = incl;
-        __syncthreads();
-        for (int q = 0; q < wv; ++q) incl += sh_wave[q];
-        const uint32_t before = incl - mine;
-        if (before < want && incl >= want) {                 // exactly one thread
-            uint32_t acc = before;
-            for (int j = 0; j < per; ++j) {
-                const int b = nb - 1 - (tid * per + j);
-                if (acc + hist[b] >= want) { sh_bin = (uint32_t)b; sh_need = want - acc; sh_count = hist[b]; break; }
-                acc += hist[b];
-            }
-        }
-        __syncthreads();
-    };
-    auto fold_copies = [&](int nb) {
-        for (int b = tid; b < nb; b += kTopkBlock) {
-            uint32_t c = hist[b];
-#pragma unroll
-            for (int q = 1; q < kTopkCopies; ++q) c += hist[q * kTopkHistStride + b];
-            hist[b] = c;
-        }
-        __syncthreads();
-    };
-    // Short cut (keys in registers): the k-th largest of the 1024 per-thread maxima is a lower bound of the k-th
-    // largest element, and on anything but heavily tied rows only a few dozen elements reach its 11-bit bin.  Those
-    // go to a short list in LDS and every entry counts the entries ahead of it: its count is its output position.
-    // More than kTopkShort entries (ties, flat rows): the general radix passes below do the row.
-    if (REGS) {
-        uint32_t mx = 0;
-#pragma unroll
-        for (int j = 0; j < kTopkRegs; ++j) mx = max(mx, keys[j]);
-        for (int b = tid; b < kTopkCopies * kTopkHistStride; b += kTopkBlock) hist[b] = 0;
-        if (tid == 0) sh_short = 0;
-        __syncthreads();
-        atomicAdd(&my_hist[mx >> 21], 1u);                   // a thread without a column has mx = 0: bin 0, never needed
-        __syncthreads();
-        fold_copies(2048);
-        find_bin(2048, (uint32_t)k);
-        const uint32_t low = max(sh_bin << 21, 1u);
-        uint32_t *short_key = hist, *short_inv = hist + kTopkShort;   // the histogram is free again
-#pragma unroll
-        for (int j = 0; j < kTopkRegs; ++j)
-            if (j * kTopkBlock < n_cols && keys[j] >= low) {
-                const uint32_t pos = atomicAdd(&sh_short, 1u);
-                if (pos < kTopkShort) {
-                    short_key[pos] = keys[j];
-                    short_inv[pos] = 0xFFFFFFFFu - (uint32_t)(j * kTopkBlock + tid);
-                }
-            }
-        __syncthreads();
-        LGC_TOPK_STAMP(2);
-        const uint32_t n_short = sh_short;
-        if (n_short <= kTopkShort) {
-            if (wv * kWave < (int)n_short) {                 // whole wavefronts past the list have nothing to rank
-                const uint32_t kt = tid < (int)n_short ? short_key[tid] : 0u, it = tid < (int)n_short ? short_inv[tid] : 0u;
-                uint32_t ahead = 0;
-                for (uint32_t c0 = 0; c0 < n_short; c0 += 8) {   // broadcast reads, eight entries in flight; slots past
-                    uint32_t kc[8], ic[8];                       // the list end read as 0 = behind every entry
-#pragma unroll
-                    for (int q = 0; q < 8; ++q) {
-                        const bool in = c0 + q < n_short;
-                        kc[q] = in ? short_key[c0 + q] : 0u;
-                        ic[q] = in ? short_inv[c0 + q] : 0u;
-                    }
-#pragma unroll
-                    for (int q = 0; q < 8; ++q) ahead += (kc[q] > kt || (kc[q] == kt && ic[q] > it)) ? 1u : 0u;
-                }
-                if (tid < (int)n_short && ahead < (uint32_t)k) {
-                    const uint32_t idx = 0xFFFFFFFFu - it;
-                    out_index[(int64_t)blockIdx.x * k + ahead] = (int64_t)idx;
-                    if (out_value)
-                        out_value[(int64_t)blockIdx.x * k + ahead] =
-                            masked_at(srow[idx], MASK == 1 ? mrow[idx] : 0.0f, (int)idx);
-                }
-            }
-            LGC_TOPK_STAMP(12);
-            return;
-        }
-        __syncthreads();
-    }
-    uint32_t prefix = 0, mask = 0, need = (uint32_t)k, eq_total = 0;
-    const int shifts[3] = {21, 10, 0}, bits[3] = {11, 11, 10};
-    for (int pass = 0; pass < 3; ++pass) {
-        const int shift = shifts[pass], nb = 1 << bits[pass];
-        for (int b = tid; b < kTopkCopies * kTopkHistStride; b += kTopkBlock) hist[b] = 0;
-        __syncthreads();
-        if (REGS) {
-#pragma unroll
-            for (int j = 0; j < kTopkRegs; ++j)
-                if (j * kTopkBlock < n_cols && (keys[j] & mask) == prefix)
-                    atomicAdd(&my_hist[(keys[j] >> shift) & (nb - 1)], 1u);
-        } else {
-            for (int base = 0; base < n_cols; base += 4 * kTopkBlock) {   // four independent loads per thread in flight
-                float sv[4], mv[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int i = min(base + j * kTopkBlock + tid, n_cols - 1);
-                    sv[j] = srow[i];
-                    mv[j] = MASK == 1 ? mrow[i] : 0.0f;
-                }
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int i = base + j * kTopkBlock + tid;
-                    const uint32_t key = key_of(sv[j], mv[j], i);
-                    if (i < n_cols && (key & mask) == prefix) atomicAdd(&my_hist[(key >> shift) & (nb - 1)], 1u);
-                }
-            }
-        }
-        __syncthreads();
-        LGC_TOPK_STAMP(2 + 3 * pass);
-        fold_copies(nb);                               // into copy 0
-        LGC_TOPK_STAMP(3 + 3 * pass);
-        find_bin(nb, need);
-        prefix |= sh_bin << shift;
-        mask |= (uint32_t)(nb - 1) << shift;
-        need = sh_need;
-        eq_total = sh_count;
-        __syncthreads();
-        LGC_TOPK_STAMP(4 + 3 * pass);
-    }
-    const uint32_t T = prefix, n_gt = (uint32_t)k - need;   // take all keys > T (n_gt of them) and `need` keys == T
-    if (tid == 0) sh_count = 0;
-    for (int i = tid; i < kTopkMax; i += kTopkBlock) cand_key[i] = cand_inv[i] = 0u;
-    __syncthreads();
-    const bool ties_cut = eq_total > need;                  // more elements equal T than fit: lowest indices win
-    uint32_t eq_taken = 0;                                  // block-uniform, only used when ties_cut
-    auto collect = [&](int i, uint32_t key) {   // key 0 marks a slot past the row end (T >= 1 whenever k <= n_cols)
-        const bool gt = key > T, eq = key == T;
-        if (gt || (eq && !ties_cut)) {
-            const uint32_t pos = atomicAdd(&sh_count, 1u);
-            cand_key[pos] = key;
-            cand_inv[pos] = 0xFFFFFFFFu - (uint32_t)i;
-        }
-        if (ties_cut && eq_taken < need) {   // ordered by index: ballots + per-wave offsets (rare: exact ties at the cut)
-            const unsigned long long bal = __ballot(eq);
-            if (lane == 0) sh_wave[wv] = (uint32_t)__popcll(bal);
-            __syncthreads();
-            uint32_t off = eq_taken, tot = 0;
-            for (int q = 0; q < kTopkBlock / kWave; ++q) { if (q < wv) off += sh_wave[q]; tot += sh_wave[q]; }
-            const uint32_t rank = off + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
-            if (eq && rank < need) {
-                cand_key[n_gt + rank] = key;
-                cand_inv[n_gt + rank] = 0xFFFFFFFFu - (uint32_t)i;
-            }
-            eq_taken += tot;
-            __syncthreads();
-        }
-    };
-    if (REGS) {
-#pragma unroll
-        for (int j = 0; j < kTopkRegs; ++j)
-            if (j * kTopkBlock < n_cols) collect(j * kTopkBlock + tid, keys[j]);   // block-uniform condition
-    } else {
-        for (int base = 0; base < n_cols; base += kTopkBlock) {
-            const int i = base + tid;
-            const int ic = min(i, n_cols - 1);
-            collect(i, key_of(srow[ic], MASK == 1 ? mrow[ic] : 0.0f, i));
-        }
-    }
-    __syncthreads();
-    LGC_TOPK_STAMP(11);
-    // bitonic sort, descending, of the first n_sort >= k candidate slots (unused slots are 0 = below every real key)
-    int n_sort = 2;
-    while (n_sort < k) n_sort <<= 1;
-    for (int size = 2; size <= n_sort; size <<= 1) {
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-            const int a = tid, b = tid ^ stride;
-            if (a < n_sort && b > a) {
-                const bool desc = (a & size) == 0;
-                const uint32_t xk = cand_key[a], yk = cand_key[b], xi = cand_inv[a], yi = cand_inv[b];
-                const bool x_lt_y = xk < yk || (xk == yk && xi < yi);
-                const bool differ = xk != yk || xi != yi;
-                if (differ && (desc ? x_lt_y : !x_lt_y)) {
-                    cand_key[a] = yk; cand_inv[a] = yi;
-                    cand_key[b] = xk; cand_inv[b] = xi;
-                }
-            }
-            __syncthreads();
-        }
-    }
-    LGC_TOPK_STAMP(12);
-    if (tid < k) {
-        const uint32_t idx = 0xFFFFFFFFu - cand_inv[tid];
-        out_index[(int64_t)blockIdx.x * k + tid] = (int64_t)idx;
-        if (out_value)
-            out_value[(int64_t)blockIdx.x * k + tid] = masked_at(srow[idx], MASK == 1 ? mrow[idx] : 0.0f, (int)idx);
-    }
-}
-
-// ----------------------------------------------------------------------------------------
-// Mini-batch sampler
-// ----------------------------------------------------------------------------------------
-// splitmix64 finaliser as a counter-based generator: draw(seed, step, sample, attempt) is stateless.
-__device__ __forceinline__ uint64_t mix64(uint64_t z) {
-    z += 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
-// unbiased integer in [0, range): 64-bit multiply-high of a 64-bit draw (bias < range / 2^64)
-__device__ __forceinline__ uint64_t bounded(uint64_t r, uint64_t range) { return __umul64hi(r, range); }
-
-__global__ void k_sample_triples(const int64_t *__restrict__ users, int64_t n, const int32_t *__restrict__ pos_ptr,
-                                 const int64_t *__restrict__ pos_items, const int32_t *__restrict__ ign_ptr,
-                                 const int64_t *__restrict__ ign_items, int64_t n_users, int64_t n_items,
-                                 uint64_t seed, uint64_t step, int64_t *__restrict__ pos_out,
-                                 int64_t *__restrict__ neg_out, int32_t *__restrict__ status) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int64_t u = users[i];
-    const uint64_t key = mix64(mix64(seed) ^ mix64(step * 0xD1B54A32D192ED03ull + (uint64_t)i));
-    if (u < 0 || u >= n_users || pos_ptr[u + 1] == pos_ptr[u]) {
-        atomicOr(status, LGC_ST_INDEX_OOB);
-        pos_out[i] = neg_out[i] = n_users;
-        return;
-    }
-    const int32_t pb = pos_ptr[u], pc = pos_ptr[u + 1] - pb;
-    pos_out[i] = pos_items[pb + (int64_t)bounded(mix64(key), (uint64_t)pc)];
-    const int32_t ib = ign_ptr[u], ie = ign_ptr[u + 1];
-    int64_t cand = n_users;
-    bool ok = false;
-    for (int attempt = 0; attempt < 256 && !ok; ++attempt) {
-        cand = n_users + (int64_t)bounded(mix64(key + 0x632BE59BD9B4E019ull * (uint64_t)(attempt + 1)), (uint64_t)n_items);
-        int32_t lo = ib, hi = ie;                       // binary search in the sorted ignore set
-        while (lo < hi) {
-            const int32_t mid = lo + ((hi - lo) >> 1);
-            if (ign_items[mid] < cand) lo = mid + 1; else hi = mid;
-        }
-        ok = !(lo < ie && ign_items[lo] == cand);
-    }
-    if (!ok) atomicOr(status, LGC_ST_SAMPLER_EXHAUSTED);
-    neg_out[i] = cand;
 }
 
 // ----------------------------------------------------------------------------------------
@@ -2365,6 +1631,17 @@ int dispatch_dim(const DimCfg &cfg, F &&f) {
 }
 
 bool aligned_to(const void *p, size_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
+
+// The table triple of a hop entry point -- x gathered, y written, r the optional epilogue term (r_stride counts only with
+// r) -- as rows of `dim` floats, `stride` floats apart: LGC_E_INVAL for a missing table or a stride below the width,
+// else LGC_E_ALIGN.  dwordx4 accesses need only dword alignment on gfx950; 16-byte aligned rows (D % 4 == 0, torch
+// allocations) are the fast case, nothing else is rejected.
+int check_tables(const float *x, int64_t x_stride, const float *y, int64_t y_stride, const float *r, int64_t r_stride,
+                 int32_t dim) {
+    if (!x || !y || x_stride < dim || y_stride < dim || (r && r_stride < dim)) return LGC_E_INVAL;
+    if (!aligned_to(x, 4) || !aligned_to(y, 4) || (r && !aligned_to(r, 4))) return LGC_E_ALIGN;
+    return 0;
+}
 
 }  // namespace
 
@@ -2698,17 +1975,6 @@ const Knobs &knobs() {
     return k;
 }
 
-// The opt-in for more than 64 KiB of dynamic LDS is per DEVICE: remember it per device ordinal.
-int allow_big_lds(const void *fn, int bytes, unsigned long long *done_mask) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = -1;
-    if (dev >= 0 && ((*done_mask >> dev) & 1ull)) return 0;
-    const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    if (e != hipSuccess) return (int)e;
-    if (dev >= 0) *done_mask |= 1ull << dev;
-    return 0;
-}
-
 // Arguments of one tile class + whether the DPP/buffer fast path applies (see lgc_spmm_tiles).
 struct TilePrep {
     TileArgs p;
@@ -2737,10 +2003,10 @@ int prepare_tiles(TilePrep &out, const int32_t *order, const int32_t *meta, cons
                   int32_t tiles_per_wave, int64_t table_rows, const float *x, int64_t x_stride, float *y,
                   int64_t y_stride, const float *r, int64_t r_stride, float a, float b, int32_t dim) {
     if (dim < 4 || dim > 256) return LGC_E_DIM;
-    if (!order || !slab || !x || !y || n_tiles < 0 || tiles_per_wave < 1 || x == y) return LGC_E_INVAL;
+    if (!order || !slab || n_tiles < 0 || tiles_per_wave < 1 || x == y) return LGC_E_INVAL;
     if (width != 8 && width != 16 && width != 32) return LGC_E_INVAL;
-    if (x_stride < dim || y_stride < dim || (r && r_stride < dim)) return LGC_E_INVAL;
-    if (!aligned_to(x, 4) || !aligned_to(y, 4) || (r && !aligned_to(r, 4)) || !aligned_to(slab, 16)) return LGC_E_ALIGN;
+    if (const int rc = check_tables(x, x_stride, y, y_stride, r, r_stride, dim)) return rc;
+    if (!aligned_to(slab, 16)) return LGC_E_ALIGN;
     TileArgs p{};
     p.order = order;
     p.slab = reinterpret_cast<const u4 *>(slab);
@@ -3010,15 +2276,11 @@ int lgc_spmm(const int32_t *rowptr, const lgc_entry *entries, int32_t row_begin,
              float b, int32_t dim, void *stream_) {
     DimCfg cfg;
     if (!dim_cfg(dim, &cfg)) return LGC_E_DIM;
-    if (!rowptr || !x || !y || row_begin < 0 || row_end < row_begin || n_chunks < 0 || n_multi < 0 || short_max < 0 ||
-        table_rows < row_end)
+    if (!rowptr || row_begin < 0 || row_end < row_begin || n_chunks < 0 || n_multi < 0 || short_max < 0 ||
+        table_rows < row_end || x == y)
         return LGC_E_INVAL;
     if ((n_chunks > 0 && !chunks) || (n_multi > 0 && (!multi || !partials))) return LGC_E_INVAL;
-    if (x_stride < dim || y_stride < dim || (r && r_stride < dim)) return LGC_E_INVAL;
-    if (x == y) return LGC_E_INVAL;
-    // dwordx4 accesses need only dword alignment on gfx950; 16-byte aligned rows (D % 4 == 0, torch
-    // allocations) are the fast case, nothing else is rejected
-    if (!aligned_to(x, 4) || !aligned_to(y, 4) || (r && !aligned_to(r, 4))) return LGC_E_ALIGN;
+    if (const int rc = check_tables(x, x_stride, y, y_stride, r, r_stride, dim)) return rc;
     hipStream_t stream = as_stream(stream_);
     SpmmArgs p{rowptr, entries, x, y, r, x_stride, y_stride, r_stride, a, b, dim, cfg.lpr, row_begin, row_end,
                short_max, 0};
@@ -3049,9 +2311,8 @@ int lgc_spmm_rows(const int32_t *rowptr, const lgc_entry *entries, int32_t row_b
                   int64_t r_stride, float a, float b, int32_t dim, void *stream_) {
     DimCfg cfg;
     if (!dim_cfg(dim, &cfg)) return LGC_E_DIM;
-    if (!rowptr || !x || !y || row_begin < 0 || row_end < row_begin || table_rows < row_end || n_ids < 0 || x == y) return LGC_E_INVAL;
-    if (x_stride < dim || y_stride < dim || (r && r_stride < dim)) return LGC_E_INVAL;
-    if (!aligned_to(x, 4) || !aligned_to(y, 4) || (r && !aligned_to(r, 4))) return LGC_E_ALIGN;
+    if (!rowptr || row_begin < 0 || row_end < row_begin || table_rows < row_end || n_ids < 0 || x == y) return LGC_E_INVAL;
+    if (const int rc = check_tables(x, x_stride, y, y_stride, r, r_stride, dim)) return rc;
     if (n_ids == 0) return 0;
     if (!row_ids || !entries) return LGC_E_INVAL;
     SpmmArgs p{rowptr, entries, x, y, r, x_stride, y_stride, r_stride, a, b, dim, cfg.lpr, row_begin, row_end, 0, 0};
@@ -3069,10 +2330,9 @@ int lgc_spmm_rows_split(const int32_t *rowptr, const lgc_entry *entries, int32_t
                         float *partials, int64_t partial_rows, void *stream_) {
     DimCfg cfg;
     if (!dim_cfg(dim, &cfg)) return LGC_E_DIM;
-    if (!rowptr || !x || !y || row_begin < 0 || row_end < row_begin || table_rows < row_end || n_ids < 0 || x == y) return LGC_E_INVAL;
-    if (x_stride < dim || y_stride < dim || (r && r_stride < dim)) return LGC_E_INVAL;
+    if (!rowptr || row_begin < 0 || row_end < row_begin || table_rows < row_end || n_ids < 0 || x == y) return LGC_E_INVAL;
     if (y_rows < (compact ? n_ids : (int64_t)row_end)) return LGC_E_INVAL;
-    if (!aligned_to(x, 4) || !aligned_to(y, 4) || (r && !aligned_to(r, 4))) return LGC_E_ALIGN;
+    if (const int rc = check_tables(x, x_stride, y, y_stride, r, r_stride, dim)) return rc;
     if (n_ids == 0) return 0;
     if (!row_ids || !entries || !work || !partials) return LGC_E_INVAL;
     // every list position may end its row with a short chunk: at least one partial row per position and one to spare;
@@ -3281,15 +2541,11 @@ int lgc_spmm_tiles(const int32_t *order, const int32_t *meta, const lgc_entry *s
     if (n_tiles == 0) return 0;
     hipStream_t stream = as_stream(stream_);
     const dim3 grid((unsigned)tp.blocks);
-    if (tp.fast) {
-        if (width == 8) hipLaunchKernelGGL((k_rows_tile_dpp<8, 1>), grid, dim3(kBlock), 0, stream, tp.p);
-        else if (width == 16) hipLaunchKernelGGL((k_rows_tile_dpp<16, 1>), grid, dim3(kBlock), 0, stream, tp.p);
-        else hipLaunchKernelGGL((k_rows_tile_dpp<32, 2>), grid, dim3(kBlock), 0, stream, tp.p);
-    } else {
-        if (width == 8) hipLaunchKernelGGL((k_rows_tile<8, 1>), grid, dim3(kBlock), 0, stream, tp.p);
-        else if (width == 16) hipLaunchKernelGGL((k_rows_tile<16, 1>), grid, dim3(kBlock), 0, stream, tp.p);
-        else hipLaunchKernelGGL((k_rows_tile<32, 2>), grid, dim3(kBlock), 0, stream, tp.p);
-    }
+    with_tile_width(width, [&](auto w, auto l) {
+        constexpr int W = decltype(w)::value, L = decltype(l)::value;
+        if (tp.fast) hipLaunchKernelGGL((k_rows_tile_dpp<W, L>), grid, dim3(kBlock), 0, stream, tp.p);
+        else hipLaunchKernelGGL((k_rows_tile<W, L>), grid, dim3(kBlock), 0, stream, tp.p);
+    });
     return (int)hipGetLastError();
 }
 
@@ -3624,7 +2880,7 @@ void lgc_sweep_dplan_free(lgc_sweep_dplan *plan) { delete plan; }
 // A table the sweep kernels can address: 24-bit row ids, 32-bit byte offsets, and the padding id 0xFFFFFF out of range.
 static bool sweep_table_ok(int32_t dim, int64_t table_rows, int64_t x_stride) {
     if (table_rows <= 0 || table_rows >= 0xFFFFFF || x_stride < dim) return false;
-    const int64_t bytes = ((table_rows - 1) * x_stride + dim) * 4;
+    const int64_t bytes = table_bytes(table_rows, x_stride, dim);
     const uint32_t pad = (uint32_t)(0xFFFFFFull * (uint64_t)(x_stride * 4));
     return x_stride * 4 < (1 << 24) && bytes < (int64_t(1) << 32) && (int64_t)pad >= bytes;
 }
@@ -3645,19 +2901,18 @@ int lgc_spmm_sweep(const uint32_t *slabs, const int32_t *wave_slab_ptr, const in
         return LGC_E_INVAL;
     if (groups == 0) groups = 4;
     if (lgc_sweep_ok(dim, table_rows, x_stride) != groups) return LGC_E_DIM;    // the plan's step width must fit the table
-    if (y_stride < dim || (r && r_stride < dim)) return LGC_E_INVAL;
-    if (!aligned_to(x, 4) || !aligned_to(y, 4) || (r && !aligned_to(r, 4)) || !aligned_to(slabs, 16) || !aligned_to(partials, 16))
-        return LGC_E_ALIGN;
+    if (const int rc = check_tables(x, x_stride, y, y_stride, r, r_stride, dim)) return rc;
+    if (!aligned_to(slabs, 16) || !aligned_to(partials, 16)) return LGC_E_ALIGN;
     hipStream_t stream = as_stream(stream_);
     const size_t lds = (size_t)(kBlock / kWave) * (size_t)(row_cap + 1) * (groups == 2 ? kWideRow : 64) * sizeof(float);
     if (lds > 160 * 1024) return LGC_E_INVAL;
     if (n_waves > 0) {
         SweepArgs p{reinterpret_cast<const u4 *>(slabs), wave_slab_ptr, wave_npieces, piece_slot, x, partials, x_stride,
-                    (uint32_t)(((table_rows - 1) * x_stride + dim) * 4), dim, row_cap, (int32_t)n_waves, 0, nullptr, dim, 0};
+                    (uint32_t)table_bytes(table_rows, x_stride, dim), dim, row_cap, (int32_t)n_waves, 0, nullptr, dim, 0};
         const bool two_pass = groups == 4 && dim > 64;   // columns [0, 64) and [64, dim) as two sweeps of the same plan
         if (two_pass) {
             p.dim = 64;
-            p.x_bytes = (uint32_t)(((table_rows - 1) * x_stride + 64) * 4);
+            p.x_bytes = (uint32_t)table_bytes(table_rows, x_stride, 64);
         }
 #ifdef LGC_SWEEP_TRACE   /* debug builds only (tools/sweep_trace.py): the variable carries a device address */
         if (const char *tr = getenv("LGCN_SWEEP_TRACE")) p.trace = reinterpret_cast<unsigned long long *>(strtoull(tr, nullptr, 0));
@@ -3677,7 +2932,7 @@ int lgc_spmm_sweep(const uint32_t *slabs, const int32_t *wave_slab_ptr, const in
                 SweepArgs q = p;
                 q.x = x + 64;
                 q.dim = dim - 64;
-                q.x_bytes = (uint32_t)(((table_rows - 1) * x_stride + (dim - 64)) * 4);
+                q.x_bytes = (uint32_t)table_bytes(table_rows, x_stride, dim - 64);
                 q.pcol = 64;
                 hipLaunchKernelGGL(k_sweep<kSweepDepth>, dim3(blocks), dim3(kBlock), lds, stream, q);
             }
@@ -3813,81 +3068,6 @@ int lgc_hop_exchange(const lgc_operator *item_op, const lgc_operator *user_op, i
     return lgc_apply(user_op, table_rows, x, x_stride, y, y_stride, r, r_stride, a, b, dim, stream);
 }
 
-int lgc_segment_sum(const int64_t *key_sorted, const int64_t *dest, const float *vals, const int32_t *vals_index, int64_t n,
-                    float scale, float *y, int64_t y_stride, int64_t y_rows, int32_t dim, int32_t accumulate, void *stream_) {
-    if (!y || n < 0 || y_rows < 0 || dim < 1 || dim > 256 || y_stride < dim) return LGC_E_INVAL;
-    if (n == 0) return 0;
-    if (!key_sorted || !dest || !vals) return LGC_E_INVAL;
-    const int groups = kWave / ((dim + 3) / 4);
-    hipLaunchKernelGGL(k_segment_sum, dim3(ceil_div(n, (int64_t)(kBlock / kWave) * groups)), dim3(kBlock), 0, as_stream(stream_),
-                       key_sorted, dest, vals, vals_index, n, scale, y, y_stride, y_rows, dim, accumulate);
-    return (int)hipGetLastError();
-}
-
-int lgc_seed_prepare(const int64_t *rows, int64_t m, int64_t split, int64_t n_nodes, int64_t *rows_sorted, int32_t *perm,
-                     int64_t *dest_item, int64_t *dest_slot, int64_t *dest_user, uint8_t *col_flag, int32_t *col_slot,
-                     uint64_t *scratch, void *stream_) {
-    if (m < 0 || m > LGC_SEED_MAX) return LGC_E_RANGE;
-    if (split < 0 || n_nodes < split || (col_flag != nullptr) != (col_slot != nullptr)) return LGC_E_INVAL;
-    if (m == 0) return 0;
-    if (!rows || !rows_sorted || !perm || !dest_item || !dest_slot || !dest_user || !scratch) return LGC_E_INVAL;
-    hipStream_t st = as_stream(stream_);
-    hipLaunchKernelGGL(k_seed_rank, dim3(ceil_div(m, kRankKeys)), dim3(kBlock), 0, st, rows, (int32_t)m, n_nodes,
-                       reinterpret_cast<unsigned long long *>(scratch));
-    hipLaunchKernelGGL(k_seed_finish, dim3(ceil_div(m, kBlock)), dim3(kBlock), 0, st,
-                       reinterpret_cast<const unsigned long long *>(scratch), (int32_t)m, split, rows_sorted, perm, dest_item,
-                       dest_slot, dest_user, col_flag, col_slot);
-    return (int)hipGetLastError();
-}
-
-int lgc_seed_flags(const int64_t *rows_sorted, int64_t m, int64_t split, uint8_t *col_flag, int32_t value, void *stream_) {
-    if (m < 0 || split < 0 || value < 0 || value > 255) return LGC_E_INVAL;
-    if (m == 0) return 0;
-    if (!rows_sorted || !col_flag) return LGC_E_INVAL;
-    hipLaunchKernelGGL(k_seed_flags, dim3(ceil_div(m, kBlock)), dim3(kBlock), 0, as_stream(stream_), rows_sorted, m, split,
-                       col_flag, (uint8_t)value);
-    return (int)hipGetLastError();
-}
-
-int lgc_pair_dot_rows(const float *emb, int64_t stride, int32_t dim, int64_t n_nodes, const int64_t *idx0, const int64_t *idx1,
-                      int64_t n_pairs, float *scores, float *rows0, float *rows1, uint8_t *ok, int32_t *status, void *stream_) {
-    if (!emb || !status || dim < 1 || stride < dim || n_nodes < 0 || n_pairs < 0) return LGC_E_INVAL;
-    if (n_pairs == 0) return 0;
-    if (!idx0 || !idx1 || !scores) return LGC_E_INVAL;
-    hipLaunchKernelGGL(k_pair_dot_rows, dim3(ceil_div(n_pairs, kBlock / kWave)), dim3(kBlock), 0, as_stream(stream_), emb, stride,
-                       dim, n_nodes, idx0, idx1, n_pairs, scores, rows0, rows1, ok, status);
-    return (int)hipGetLastError();
-}
-
-int lgc_pair_seed_vals(const float *grad_scores, const uint8_t *mask, const float *grad_scale, const float *rows0,
-                       const float *rows1, int64_t n_pairs, int32_t dim, float *vals, void *stream_) {
-    if (n_pairs < 0 || dim < 1) return LGC_E_INVAL;
-    if (n_pairs == 0) return 0;
-    if (!grad_scores || !rows0 || !rows1 || !vals) return LGC_E_INVAL;
-    hipLaunchKernelGGL(k_pair_seed_vals, dim3(ceil_div(n_pairs * dim, kBlock)), dim3(kBlock), 0, as_stream(stream_), grad_scores,
-                       mask, grad_scale, rows0, rows1, n_pairs, dim, vals);
-    return (int)hipGetLastError();
-}
-
-int lgc_bpr_loss(const float *scores, const uint8_t *mask, int64_t n_triples, int64_t size, float *loss, float *grad,
-                 void *stream_) {
-    if (!loss || n_triples < 0 || size <= 0) return LGC_E_INVAL;
-    if (n_triples > 0 && (!scores || !grad)) return LGC_E_INVAL;
-    hipLaunchKernelGGL(k_bpr_loss, dim3(1), dim3(kSeedBlock), 0, as_stream(stream_), scores, mask, n_triples,
-                       1.0f / (float)size, loss, grad);
-    return (int)hipGetLastError();
-}
-
-int lgc_reg_rows(const float *w, int64_t stride, int32_t dim, int64_t n_rows, const int64_t *ids0, int64_t m0, const int64_t *ids1,
-                 int64_t m1, const int64_t *ids2, int64_t m2, float scale, float *value, int64_t *rows_out, int32_t *status,
-                 void *stream_) {
-    if (!w || !value || !status || dim < 1 || stride < dim || n_rows < 0 || m0 < 0 || m1 < 0 || m2 < 0) return LGC_E_INVAL;
-    if ((m0 > 0 && !ids0) || (m1 > 0 && !ids1) || (m2 > 0 && !ids2)) return LGC_E_INVAL;
-    hipLaunchKernelGGL(k_reg_rows, dim3(1), dim3(kSeedBlock), 0, as_stream(stream_), w, stride, dim, n_rows, ids0, m0, ids1, m1, ids2,
-                       m2, scale, value, rows_out, status);
-    return (int)hipGetLastError();
-}
-
 int lgc_seed_mark(const int32_t *rowptr, const lgc_entry *entries, int32_t row_begin, int32_t row_end, const int64_t *seed_rows,
                   int64_t n_seed, uint8_t *mark, int64_t mark_len, int32_t value, void *stream_) {
     if (n_seed < 0 || row_begin < 0 || row_end < row_begin || mark_len < 0 || value < 0 || value > 255) return LGC_E_INVAL;
@@ -3904,11 +3084,11 @@ int lgc_seed_pull(const int32_t *rowptr, const lgc_entry *entries, int32_t row_b
                   int64_t seed_stride, int64_t table_rows, float *y, int64_t y_stride, int32_t dim, void *stream_) {
     DimCfg cfg;
     if (!dim_cfg(dim, &cfg)) return LGC_E_DIM;
-    if (!rowptr || !col_flag || !col_slot || !seed_vals || !y || row_begin < 0 || row_end < row_begin || n_chunks < 0 ||
-        n_multi < 0 || short_max < 0 || table_rows < row_end || seed_stride < dim || y_stride < dim)
+    if (!rowptr || !col_flag || !col_slot || row_begin < 0 || row_end < row_begin || n_chunks < 0 || n_multi < 0 ||
+        short_max < 0 || table_rows < row_end)
         return LGC_E_INVAL;
     if ((n_chunks > 0 && !chunks) || (n_multi > 0 && (!multi || !partials))) return LGC_E_INVAL;
-    if (!aligned_to(seed_vals, 4) || !aligned_to(y, 4)) return LGC_E_ALIGN;
+    if (const int rc = check_tables(seed_vals, seed_stride, y, y_stride, nullptr, 0, dim)) return rc;
     hipStream_t stream = as_stream(stream_);
     SpmmArgs p{rowptr, entries, seed_vals, y, nullptr, seed_stride, y_stride, 0, 1.0f, 0.0f, dim, cfg.lpr, row_begin, row_end,
                short_max, 0, col_flag, col_slot, row_mark};
@@ -3953,101 +3133,5 @@ int lgc_lincomb(float *y, int64_t y_stride, const float *const *src, const int64
     hipLaunchKernelGGL(k_lincomb, dim3(blocks), dim3(kBlock), 0, as_stream(stream_), y, y_stride, a, n_rows, dim);
     return (int)hipGetLastError();
 }
-
-static int adam_launch(float *w, const float *g, float *m, float *v, int64_t n, float one_minus_beta1, float beta2,
-                       float one_minus_beta2, float eps, float step_size, float bias_correction2_sqrt, const float *hyper,
-                       void *stream_);
-
-int lgc_adam_step(float *w, const float *g, float *m, float *v, int64_t n, float one_minus_beta1, float beta2,
-                  float one_minus_beta2, float eps, float step_size, float bias_correction2_sqrt, void *stream_) {
-    if (!(bias_correction2_sqrt > 0.0f)) return LGC_E_INVAL;
-    return adam_launch(w, g, m, v, n, one_minus_beta1, beta2, one_minus_beta2, eps, step_size, bias_correction2_sqrt, nullptr,
-                       stream_);
-}
-
-int lgc_adam_step_hp(float *w, const float *g, float *m, float *v, int64_t n, const float *hyper, void *stream_) {
-    if (!hyper) return LGC_E_INVAL;
-    return adam_launch(w, g, m, v, n, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 1.0f, hyper, stream_);
-}
-
-static int adam_launch(float *w, const float *g, float *m, float *v, int64_t n, float one_minus_beta1, float beta2,
-                       float one_minus_beta2, float eps, float step_size, float bias_correction2_sqrt, const float *hyper,
-                       void *stream_) {
-    if (!w || !g || !m || !v || n < 0) return LGC_E_INVAL;
-    // dword-aligned, and all four at the same offset inside a 16-byte line (a row range of same-shaped tables whose rows
-    // are not whole float4s, e.g. rows [lo, hi) of a [N, 90] table): the first elements up to the line are done one by one
-    const uintptr_t mis = reinterpret_cast<uintptr_t>(w) & 15;
-    if ((mis & 3) != 0 || (reinterpret_cast<uintptr_t>(g) & 15) != mis || (reinterpret_cast<uintptr_t>(m) & 15) != mis ||
-        (reinterpret_cast<uintptr_t>(v) & 15) != mis)
-        return LGC_E_ALIGN;
-    if (n == 0) return 0;
-    hipStream_t stream = as_stream(stream_);
-    const int64_t head = std::min<int64_t>(n, (int64_t)((16 - mis) & 15) / 4);
-    if (head > 0)
-        hipLaunchKernelGGL(k_adam, dim3(1), dim3(kBlock), 0, stream, w, g, m, v, (int64_t)0, head, beta2, one_minus_beta1,
-                           one_minus_beta2, eps, step_size, bias_correction2_sqrt, hyper);
-    w += head; g += head; m += head; v += head; n -= head;
-    if (n == 0) return (int)hipGetLastError();
-    const int64_t n4 = n / 4;
-    const int64_t blocks = std::max<int64_t>(ceil_div(n4, (int64_t)kBlock * kAdamU), 1);
-    if (blocks >= INT32_MAX) return LGC_E_RANGE;
-    hipLaunchKernelGGL(k_adam, dim3((unsigned)blocks), dim3(kBlock), 0, stream, w, g, m, v, n4, n, beta2,
-                       one_minus_beta1, one_minus_beta2, eps, step_size, bias_correction2_sqrt, hyper);
-    return (int)hipGetLastError();
-}
-
-int lgc_pair_dot(const float *emb, int64_t stride, int32_t dim, int64_t n_nodes, const int64_t *idx0,
-                 const int64_t *idx1, int64_t n_pairs, float *scores, int32_t *status, void *stream_) {
-    if (!emb || !status || dim < 1 || stride < dim || n_nodes < 0 || n_pairs < 0) return LGC_E_INVAL;
-    if (n_pairs == 0) return 0;
-    if (!idx0 || !idx1 || !scores) return LGC_E_INVAL;
-    hipLaunchKernelGGL(k_pair_dot, dim3(ceil_div(n_pairs, kBlock / kWave)), dim3(kBlock), 0, as_stream(stream_), emb,
-                       stride, dim, n_nodes, idx0, idx1, n_pairs, scores, status);
-    return (int)hipGetLastError();
-}
-
-int lgc_mask_topk(const float *scores, int64_t score_stride, const float *seen, int64_t seen_stride, const int64_t *list_ptr,
-                  const int64_t *list_items, const int64_t *list_rows, int64_t n_rows, int32_t n_cols, int32_t k,
-                  int64_t *out_index, float *out_value, void *stream_) {
-    if (!scores || !out_index || n_rows < 0 || n_cols < 1 || k < 1 || k > n_cols || score_stride < n_cols ||
-        (seen && seen_stride < n_cols) || n_rows >= INT32_MAX || (seen && list_ptr) || (list_ptr && !list_items))
-        return LGC_E_INVAL;
-    if (k > kTopkMax) return LGC_E_RANGE;
-    const size_t lds = list_ptr ? (size_t)((n_cols + 31) / 32) * 4 : 0;
-    if (lds > 120 * 1024) return LGC_E_RANGE;             // the bitmask form holds up to 983,040 columns
-    if (n_rows == 0) return 0;
-    const bool regs = n_cols <= kTopkRegs * kTopkBlock;
-    const int mode = list_ptr ? 2 : seen ? 1 : 0;
-    using topk_fn = void (*)(const float *, int64_t, const float *, int64_t, const int64_t *, const int64_t *,
-                             const int64_t *, int32_t, int32_t, int64_t *, float *);
-    static const topk_fn kerns[2][3] = {{k_mask_topk<false, 0>, k_mask_topk<false, 1>, k_mask_topk<false, 2>},
-                                        {k_mask_topk<true, 0>, k_mask_topk<true, 1>, k_mask_topk<true, 2>}};
-    const topk_fn kern = kerns[regs][mode];
-    if (lds > 16 * 1024) {    // static LDS (histogram copies, candidates) + the bitmask can pass the 64 KiB default
-        static unsigned long long lds_ok_topk[2][3] = {};
-        const int rc_attr = allow_big_lds(reinterpret_cast<const void *>(kern), 120 * 1024, &lds_ok_topk[regs][mode]);
-        if (rc_attr != 0) return rc_attr;
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)n_rows), dim3(kTopkBlock), lds, as_stream(stream_), scores, score_stride, seen,
-                       seen_stride, list_ptr, list_items, list_rows, n_cols, k, out_index, out_value);
-    return (int)hipGetLastError();
-}
-
-int lgc_sample_triples(const int64_t *users, int64_t n, const int32_t *pos_ptr, const int64_t *pos_items,
-                       const int32_t *ign_ptr, const int64_t *ign_items, int64_t n_users, int64_t n_items, uint64_t seed,
-                       uint64_t step, int64_t *pos_out, int64_t *neg_out, int32_t *status, void *stream_) {
-    if (n < 0 || n_users < 0 || n_items < 1 || !status) return LGC_E_INVAL;
-    if (n == 0) return 0;
-    if (!users || !pos_ptr || !pos_items || !ign_ptr || !pos_out || !neg_out) return LGC_E_INVAL;
-    hipLaunchKernelGGL(k_sample_triples, dim3(ceil_div(n, kBlock)), dim3(kBlock), 0, as_stream(stream_), users, n,
-                       pos_ptr, pos_items, ign_ptr, ign_items, n_users, n_items, seed, step, pos_out, neg_out, status);
-    return (int)hipGetLastError();
-}
-
-#ifdef LGC_TOPK_TRACE
-int lgc_debug_topk_trace(unsigned long long *out16) {
-    return (int)hipMemcpyFromSymbol(out16, HIP_SYMBOL(g_topk_trace), sizeof(unsigned long long) * 16);
-}
-#endif
 
 }  // extern "C"

@@ -1,8 +1,7 @@
 #!/usr/bin/env python3
 """Phase times of k_mask_topk for one request row (debug build with -DLGC_TOPK_TRACE, see the build line below).
-Build:  hipcc -O3 -std=c++17 --offload-arch=gfx950 -ffp-contract=off -fPIC -Iinclude -DLGC_TOPK_TRACE -shared \
-            -o tools/_dbg/liblgconv_trace.so gnn-ecommerce_amd/csrc/lgconv_hip.hip
-Run:    LGCN_LIB_PATH=tools/_dbg/liblgconv_trace.so python tools/topk_trace.py [n_cols]"""
+Build:  make -C gnn-ecommerce_amd/csrc EXTRA=-DLGC_TOPK_TRACE OUT=$PWD/tools/_dbg/topk_trace
+Run:    LGCN_LIB_PATH=tools/_dbg/topk_trace/liblgconv_hip.so python tools/topk_trace.py [n_cols]"""
 import ctypes, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
