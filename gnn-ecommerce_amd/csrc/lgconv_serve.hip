@@ -1,4 +1,5 @@
-// lgconv_serve.hip -- the serving tail (seen-mask + top-k per row) and the mini-batch sampler.
+// lgconv_serve.hip -- the serving tail (seen-mask + top-k per row), the mini-batch sampler and the epoch evaluation
+// (score panels, hits per row, metric sums).
 // C ABI: include/lgconv_hip.h
 #include "lgconv_common.h"
 
@@ -345,6 +346,213 @@ __global__ void k_sample_triples(const int64_t *__restrict__ users, int64_t n, c
     neg_out[i] = cand;
 }
 
+// ----------------------------------------------------------------------------------------
+// Epoch evaluation: score panels, hits per row, metric sums
+// ----------------------------------------------------------------------------------------
+// out[r, i] = sum_d users[row_ids[r], d] * items[i, d]: an fp32 GEMM whose A operand is gathered.  One workgroup owns
+// kScoreBN items: their rows are staged in LDS ONCE, for the whole width, and the workgroup then walks row tiles of
+// kScoreBM panel rows, whose user rows pass through LDS in chunks of kScoreKC columns (the next chunk is already in
+// registers while the current one is multiplied).  A thread keeps a 4 x 8 tile of sums in registers.
+// Position independence: every out[r, i] is ONE chain of v_fma_f32 over d = 0, 1, ... round_up(dim, 4) - 1 in
+// ascending order, starting from +0, with zeros in the columns past dim -- the same instructions on the same values
+// wherever the pair sits.  Tile edges only clamp or predicate LOADS (a clamped row computes a sum nobody stores).
+constexpr int kScoreBM = 64, kScoreBN = 128, kScoreKC = 32;
+constexpr int kScoreAStride = kScoreKC + 4;   // floats; (stride / 4) odd: 16 consecutive rows hit 16 different bank quads
+
+// LDS row stride (floats) of the item tile: whole float4 groups, (stride / 4) odd
+__host__ __device__ inline int score_b_stride(int dim) {
+    const int g = (dim + 3) / 4;
+    return 4 * (g | 1);
+}
+
+// Four floats of a table row starting at column d; columns >= dim read as 0 and are never touched (the row may end
+// there: padding columns, the next row, or the end of the allocation).
+__device__ __forceinline__ f4 load_row4(const float *__restrict__ row, int d, int dim, bool live) {
+    f4 v = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (live) {
+        if (d + 4 <= dim) {
+            v = *reinterpret_cast<const f4u *>(row + d);
+        } else {
+            if (d + 0 < dim) v.x = row[d + 0];
+            if (d + 1 < dim) v.y = row[d + 1];
+            if (d + 2 < dim) v.z = row[d + 2];
+        }
+    }
+    return v;
+}
+
+__global__ __launch_bounds__(kBlock) void k_score_rows(const float *__restrict__ users, int64_t user_stride,
+                                                      int64_t n_user_rows, const int64_t *__restrict__ row_ids,
+                                                      int64_t n_rows, const float *__restrict__ items,
+                                                      int64_t item_stride, int32_t n_items, int32_t dim,
+                                                      float *__restrict__ out, int64_t out_stride,
+                                                      int32_t *__restrict__ status) {
+    extern __shared__ __attribute__((aligned(16))) float score_lds[];
+    const int bs = score_b_stride(dim), dim4 = (dim + 3) & ~3, groups = dim4 / 4;
+    float *Bs = score_lds;                                   // [kScoreBN][bs]
+    float *As = Bs + kScoreBN * bs;                          // [kScoreBM][kScoreAStride]
+    int *row_ok = reinterpret_cast<int *>(As + kScoreBM * kScoreAStride);   // [kScoreBM]
+    const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
+    const int item0 = blockIdx.x * kScoreBN;
+
+    // the item tile, whole width, once per workgroup; items past the end are clamped to the last one (never stored)
+    for (int e = tid; e < kScoreBN * groups; e += kBlock) {
+        const int it = e / groups, g = e - it * groups;
+        const int64_t gi = min(item0 + it, n_items - 1);
+        *reinterpret_cast<f4 *>(Bs + it * bs + 4 * g) = load_row4(items + gi * item_stride, 4 * g, dim, true);
+    }
+
+    // staging of the user chunk: thread -> (row ar + 32 q, columns 4 ag ..) for q = 0, 1
+    const int ar = tid >> 3, ag = tid & 7;
+    const int64_t n_tiles = (n_rows + kScoreBM - 1) / kScoreBM;
+    for (int64_t tile = blockIdx.y; tile < n_tiles; tile += gridDim.y) {
+        const int64_t row0 = tile * kScoreBM;
+        const float *arow[2];
+        bool alive[2];
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            const int64_t r = min(row0 + ar + 32 * q, n_rows - 1);
+            const int64_t id = row_ids ? row_ids[r] : r;
+            alive[q] = id >= 0 && id < n_user_rows;
+            arow[q] = users + (alive[q] ? id : 0) * user_stride;
+            if (ag == 0) {
+                row_ok[ar + 32 * q] = alive[q] ? 1 : 0;
+                if (!alive[q]) atomicOr(status, LGC_ST_INDEX_OOB);
+            }
+        }
+        float acc[4][8];
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 8; ++j) acc[i][j] = 0.0f;
+        f4 stage[2];
+#pragma unroll
+        for (int q = 0; q < 2; ++q) stage[q] = load_row4(arow[q], 4 * ag, dim, alive[q] && 4 * ag < dim4);
+        for (int k0 = 0; k0 < dim4; k0 += kScoreKC) {
+            __syncthreads();                                 // the previous chunk (and, first time, nothing) is consumed
+#pragma unroll
+            for (int q = 0; q < 2; ++q)
+                *reinterpret_cast<f4 *>(As + (ar + 32 * q) * kScoreAStride + 4 * ag) = stage[q];
+            __syncthreads();                                 // also orders the item tile and row_ok before their first use
+            const int kn = k0 + kScoreKC;
+            if (kn < dim4) {
+#pragma unroll
+                for (int q = 0; q < 2; ++q) stage[q] = load_row4(arow[q], kn + 4 * ag, dim, alive[q] && kn + 4 * ag < dim4);
+            }
+            const int steps = min(kScoreKC, dim4 - k0) / 4;  // block-uniform
+            for (int s = 0; s < steps; ++s) {
+                f4 a[4], b[8];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) a[i] = *reinterpret_cast<const f4 *>(As + (ty * 4 + i) * kScoreAStride + 4 * s);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) b[j] = *reinterpret_cast<const f4 *>(Bs + (tx + 16 * j) * bs + k0 + 4 * s);
+#pragma unroll
+                for (int kk = 0; kk < 4; ++kk)
+#pragma unroll
+                    for (int i = 0; i < 4; ++i)
+#pragma unroll
+                        for (int j = 0; j < 8; ++j) acc[i][j] = __fmaf_rn(a[i][kk], b[j][kk], acc[i][j]);
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int64_t r = row0 + ty * 4 + i;
+            if (r < n_rows) {
+                const bool ok = row_ok[ty * 4 + i] != 0;     // a row whose id was out of range is zero-filled
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    const int it = item0 + tx + 16 * j;
+                    if (it < n_items) out[r * out_stride + it] = ok ? acc[i][j] : 0.0f;
+                }
+            }
+        }
+        __syncthreads();                                     // row_ok is rewritten by the next tile
+    }
+}
+
+// hits[r] = how many of topk[r, 0..k) occur in the positive list of the row's user; recall[r] = hits / list length.
+// One wavefront per row: the top-k entries sit in LDS, the lanes stride over the list and flag the entries they
+// meet (a flag, not a count: a positive listed twice still hits once, as set(a).intersection(b) upstream), the flags
+// are counted.  The list length counts duplicates (upstream's len(item_id_idx_list)); an empty list gives NaN.
+constexpr int kHitsRows = kBlock / kWave;
+
+__global__ __launch_bounds__(kBlock) void k_topk_hits(const int64_t *__restrict__ topk, int64_t topk_stride, int32_t k,
+                                                     const int64_t *__restrict__ pos_ptr,
+                                                     const int64_t *__restrict__ pos_items,
+                                                     const int64_t *__restrict__ list_rows, int64_t n_rows,
+                                                     int64_t n_users, int32_t *__restrict__ hits,
+                                                     double *__restrict__ recall, int32_t *__restrict__ status) {
+    __shared__ int64_t sh_top[kHitsRows][kTopkMax];
+    __shared__ int sh_flag[kHitsRows][kTopkMax];
+    const int lane = threadIdx.x & (kWave - 1), wv = threadIdx.x / kWave;
+    const int64_t r = (int64_t)blockIdx.x * kHitsRows + wv;
+    const bool live = r < n_rows;
+    int64_t u = 0;
+    bool ok = false;
+    if (live) {
+        u = list_rows ? list_rows[r] : r;
+        ok = u >= 0 && u < n_users;
+        for (int e = lane; e < k; e += kWave) {
+            sh_top[wv][e] = topk[r * topk_stride + e];
+            sh_flag[wv][e] = 0;
+        }
+    }
+    __syncthreads();
+    int64_t len = 0;
+    if (live && ok) {
+        const int64_t lo = pos_ptr[u], hi = pos_ptr[u + 1];
+        len = hi - lo;
+        for (int64_t p = lo + lane; p < hi; p += kWave) {
+            const int64_t it = pos_items[p];
+            for (int e = 0; e < k; ++e)
+                if (sh_top[wv][e] == it) sh_flag[wv][e] = 1;
+        }
+    }
+    __syncthreads();
+    if (live) {
+        int n = 0;
+        for (int e = lane; e < k; e += kWave) n += sh_flag[wv][e];
+        for (int off = kWave / 2; off > 0; off >>= 1) n += __shfl_down(n, off);
+        if (lane == 0) {
+            if (!ok) atomicOr(status, LGC_ST_INDEX_OOB);
+            hits[r] = ok ? n : 0;
+            recall[r] = ok ? (double)n / (double)len : 0.0;
+        }
+    }
+}
+
+// Sum of hits (int64) and of recall (double) in ONE workgroup and a fixed order: thread t adds elements t, t + 1024,
+// ... in that order, then a binary tree over the threads.  No atomics: the same bits on every run.
+constexpr int kSumBlock = 1024;
+
+__global__ __launch_bounds__(kSumBlock) void k_metric_sums(const int32_t *__restrict__ hits,
+                                                          const double *__restrict__ recall, int64_t n,
+                                                          int64_t *__restrict__ hits_sum, double *__restrict__ recall_sum) {
+    __shared__ int64_t sh_h[kSumBlock];
+    __shared__ double sh_r[kSumBlock];
+    const int tid = threadIdx.x;
+    int64_t h = 0;
+    double s = 0.0;
+    for (int64_t i = tid; i < n; i += kSumBlock) {
+        if (hits) h += hits[i];
+        if (recall) s += recall[i];
+    }
+    sh_h[tid] = h;
+    sh_r[tid] = s;
+    __syncthreads();
+    for (int half = kSumBlock / 2; half > 0; half >>= 1) {
+        if (tid < half) {
+            sh_h[tid] += sh_h[tid + half];
+            sh_r[tid] += sh_r[tid + half];
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        if (hits_sum) *hits_sum = sh_h[0];
+        if (recall_sum) *recall_sum = sh_r[0];
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -384,6 +592,53 @@ int lgc_sample_triples(const int64_t *users, int64_t n, const int32_t *pos_ptr, 
     if (!users || !pos_ptr || !pos_items || !ign_ptr || !pos_out || !neg_out) return LGC_E_INVAL;
     hipLaunchKernelGGL(k_sample_triples, dim3(ceil_div(n, kBlock)), dim3(kBlock), 0, as_stream(stream_), users, n,
                        pos_ptr, pos_items, ign_ptr, ign_items, n_users, n_items, seed, step, pos_out, neg_out, status);
+    return (int)hipGetLastError();
+}
+
+int lgc_score_rows(const float *users, int64_t user_stride, int64_t n_user_rows, const int64_t *row_ids, int64_t n_rows,
+                   const float *items, int64_t item_stride, int32_t n_items, int32_t dim, float *out, int64_t out_stride,
+                   int32_t *status, void *stream_) {
+    if (!lgc_dim_ok(dim)) return LGC_E_DIM;
+    if (!users || !items || !out || !status || n_rows < 0 || n_user_rows < 0 || n_items < 1 || user_stride < dim ||
+        item_stride < dim || out_stride < n_items)
+        return LGC_E_INVAL;
+    if (n_rows >= INT32_MAX || n_user_rows >= INT32_MAX) return LGC_E_RANGE;
+    if (n_rows == 0) return 0;
+    const size_t lds = (size_t)(kScoreBN * score_b_stride(dim) + kScoreBM * kScoreAStride) * 4 + kScoreBM * sizeof(int);
+    if (lds > 48 * 1024) {
+        static unsigned long long lds_ok_score = 0;
+        const int rc_attr = allow_big_lds(reinterpret_cast<const void *>(k_score_rows), 144 * 1024, &lds_ok_score);
+        if (rc_attr != 0) return rc_attr;
+    }
+    // enough workgroups for every CU twice over: the row tiles of a panel are split only when the item tiles are few
+    const int64_t item_tiles = ceil_div(n_items, kScoreBN), row_tiles = ceil_div(n_rows, kScoreBM);
+    const int64_t split = std::min<int64_t>(row_tiles, std::max<int64_t>(1, 512 / item_tiles));
+    hipLaunchKernelGGL(k_score_rows, dim3((unsigned)item_tiles, (unsigned)split), dim3(kBlock), lds, as_stream(stream_),
+                       users, user_stride, n_user_rows, row_ids, n_rows, items, item_stride, n_items, dim, out, out_stride,
+                       status);
+    return (int)hipGetLastError();
+}
+
+int lgc_topk_hits(const int64_t *topk, int64_t topk_stride, int32_t k, const int64_t *pos_ptr, const int64_t *pos_items,
+                  const int64_t *list_rows, int64_t n_rows, int64_t n_users, int32_t *hits, double *recall,
+                  int32_t *status, void *stream_) {
+    if (!topk || !pos_ptr || !hits || !recall || !status || n_rows < 0 || n_users < 0 || k < 1 || topk_stride < k)
+        return LGC_E_INVAL;
+    if (k > kTopkMax || n_rows >= INT32_MAX) return LGC_E_RANGE;
+    if (n_rows == 0) return 0;
+    hipLaunchKernelGGL(k_topk_hits, dim3(ceil_div(n_rows, kHitsRows)), dim3(kBlock), 0, as_stream(stream_), topk,
+                       topk_stride, k, pos_ptr, pos_items, list_rows, n_rows, n_users, hits, recall, status);
+    return (int)hipGetLastError();
+}
+
+int lgc_metric_sums(const int32_t *hits, const double *recall, int64_t n_rows, int64_t *hits_sum, double *recall_sum,
+                    void *stream_) {
+    if (n_rows < 0 || (!hits_sum && !recall_sum) || (hits_sum && n_rows > 0 && !hits) ||
+        (recall_sum && n_rows > 0 && !recall))
+        return LGC_E_INVAL;
+    if (n_rows == 0) return 0;                             // nothing to add: the sums are left as they are
+    hipLaunchKernelGGL(k_metric_sums, dim3(1), dim3(kSumBlock), 0, as_stream(stream_), hits_sum ? hits : nullptr,
+                       recall_sum ? recall : nullptr, n_rows, hits_sum, recall_sum);
     return (int)hipGetLastError();
 }
 

@@ -6,7 +6,8 @@ src/inference_lightgcn.py and torchserve/lightgcn_handler.py run unchanged
 (``embedding.weight``, ``alpha``, ``convs``, ``num_nodes`` ...), ``state_dict`` keys
 (``alpha``, ``embedding.weight``), and the methods ``get_embedding``, ``forward``,
 ``predict_link``, ``recommend``, ``recommendK``, ``MARK_MAPK``, ``link_pred_loss``,
-``recommendation_loss``.  What changes is underneath: propagation is the HIP CSR-SpMM with
+``recommendation_loss``.  ``recommend_topk`` and ``evaluateK`` are additions: the epoch's evaluation
+(``recommendK`` over all validation users, then ``MARK_MAPK``) in bounded device memory.  What changes is underneath: propagation is the HIP CSR-SpMM with
 the layer sum fused (``propagate.propagate_sum``) and pair scoring is one gather-dot kernel.
 """
 from __future__ import annotations
@@ -21,8 +22,9 @@ from torch.nn.modules.loss import _Loss
 from . import _native
 from .graph import get_graph
 from .lgconv import LGConv
-from .propagate import (TOPK_MAX, RegHook, SeenLists, bpr_loss_fused, mask_topk, pair_dot, propagate_sum,
-                        regularization_through, routable_index, scores_from_table)
+from .propagate import (DEFAULT_WORKSPACE_BYTES, TOPK_MAX, PositiveLists, RegHook, SeenLists, bpr_loss_fused, evaluate_topk,
+                        mask_topk, pair_dot, propagate_sum, recommend_topk, regularization_through, routable_index,
+                        scores_from_table)
 
 __all__ = ["LightGCN", "BPRLoss", "LGConv", "regularization_loss"]
 
@@ -185,6 +187,39 @@ class LightGCN(torch.nn.Module):
         m['recall'] = m.apply(lambda x: len(x['overlap_item']) / len(x['item_id_idx_list']), axis=1)
         m['precision'] = m.apply(lambda x: len(x['overlap_item']) / k, axis=1)
         return m['precision'].mean(), m['recall'].mean(), m
+
+    def _eval_tables(self, edge_index, edge_weight, n_users, n_items, seen, users):
+        """(user table, item table, SeenLists or None, user ids int64 on the device) for the two methods below."""
+        embeds = self._serving_embedding(edge_index, edge_weight).detach()
+        user_t, item_t = torch.split(embeds, [n_users, n_items])
+        ids = users if torch.is_tensor(users) else torch.as_tensor(list(users), dtype=torch.int64)
+        ids = ids.reshape(-1).to(device=embeds.device, dtype=torch.int64).contiguous()
+        if seen is not None and not isinstance(seen, SeenLists):         # the reference's dense mask, rows positional in users
+            seen = SeenLists.from_dense(seen, ids if torch.is_tensor(users) else users, n_users, device=embeds.device)
+        return user_t, item_t, seen, ids
+
+    def recommend_topk(self, edge_index, edge_weight, n_users, n_items, seen, users, k: int = 5,
+                       workspace_bytes: int = DEFAULT_WORKSPACE_BYTES) -> Tensor:
+        """``recommendK``'s ranking as int64 ``[len(users), k]`` item indices on the device, no DataFrame, in bounded
+        memory: scores exist one panel of ``workspace_bytes`` at a time (``propagate.recommend_topk``).  ``seen``: a
+        ``SeenLists``, the reference's dense 0/1 mask (converted once, ``SeenLists.from_dense``) or None."""
+        user_t, item_t, seen, ids = self._eval_tables(edge_index, edge_weight, n_users, n_items, seen, users)
+        return recommend_topk(user_t, ids, item_t, seen, k, workspace_bytes)
+
+    def evaluateK(self, edge_index, edge_weight, n_users, n_items, seen, users, positives, k: int = 20,
+                  workspace_bytes: int = DEFAULT_WORKSPACE_BYTES):
+        """``(precision, recall, hits)``: what ``recommendK`` + ``MARK_MAPK`` report for ``users`` (None: the users of
+        ``positives``, in its order) -- the two means as Python floats, the per-user hit counts as an int32 tensor left
+        on the device.  ``positives``: a ``PositiveLists`` or a ``*_pos_list_df``.  Scores, ranking, hits and the two
+        sums stay on the device; there is one host sync, at the end."""
+        if not isinstance(positives, PositiveLists):
+            positives = PositiveLists.from_frame(positives, n_users)
+        if users is None:
+            users = positives.users
+        user_t, item_t, seen, ids = self._eval_tables(edge_index, edge_weight, n_users, n_items, seen, users)
+        if positives.ptr.device != ids.device:
+            positives = positives.to(ids.device)
+        return evaluate_topk(user_t, item_t, seen, ids, positives, k, workspace_bytes)
 
     def link_pred_loss(self, pred: Tensor, edge_label: Tensor, **kwargs) -> Tensor:
         return torch.nn.BCEWithLogitsLoss(**kwargs)(pred, edge_label.to(pred.dtype))

@@ -907,6 +907,124 @@ class SeenLists:
     def for_users(self, users: Tensor) -> "SeenLists":
         return SeenLists(self.ptr, self.items, users)
 
+    dense_builds = 0          # CSRs built by from_dense so far (cache hits do not count)
+    _dense_cache: list = []   # [(key, mask, SeenLists)], most recent last
+
+    @classmethod
+    def from_dense(cls, interactions_t: Tensor, user_id_list, n_users: int, device=None) -> "SeenLists":
+        """The CSR of the reference's dense mask (``[n_sel, n_items]``, row r = the seen items of ``user_id_list[r]``;
+        src/utils_v2.py:92-106 + :136-137), on ``device`` (default: where the mask lives).  Users outside the list get
+        empty rows.  The list form can only say "seen": a mask with any entry other than 0 or 1 is refused (upstream's
+        matrix sums a repeated purchase to 2, where ``1 - seen`` is -1), and so is a user listed twice with different
+        rows.  Upstream passes the same mask object every epoch: the result is kept per tensor identity + version."""
+        m = interactions_t
+        if not torch.is_tensor(m) or m.dim() != 2:
+            raise TypeError("the dense mask must be a 2-D tensor")
+        ids = torch.as_tensor(user_id_list).reshape(-1).to(dtype=torch.int64, device="cpu")
+        device = torch.device(m.device if device is None else device)
+        key = (id(m), m._version, m.data_ptr(), tuple(m.shape), int(n_users), str(device), ids.numpy().tobytes())
+        for k_, m_, got in cls._dense_cache:
+            if k_ == key and m_ is m:
+                return got
+        if ids.numel() != m.size(0):
+            raise ValueError(f"the dense mask has {m.size(0)} rows for {ids.numel()} users")
+        if ids.numel() and (int(ids.min()) < 0 or int(ids.max()) >= n_users):
+            raise ValueError(f"user ids must lie in [0, {n_users})")
+        nonzero = m != 0
+        if bool((nonzero & (m != 1)).any()):
+            raise ValueError("the dense mask has entries other than 0 and 1 (a purchase counted twice?): "
+                             "the list form cannot express them")
+        ids_m = ids.to(m.device)
+        order = torch.argsort(ids_m, stable=True)                      # rows by user, first occurrence first
+        sorted_ids = ids_m[order]
+        first = torch.ones_like(sorted_ids, dtype=torch.bool)
+        first[1:] = sorted_ids[1:] != sorted_ids[:-1]
+        if not bool(first.all()):                                      # a user listed twice: its rows must agree
+            lead = order[torch.cummax(torch.where(first, torch.arange(len(order), device=m.device), 0), 0).values]
+            if not bool((nonzero[order] == nonzero[lead]).all()):
+                raise ValueError("a user appears twice in user_id_list with different mask rows")
+        rows = order[first]                                            # one mask row per distinct user, ascending by user
+        r, c = nonzero[rows].nonzero(as_tuple=True)                    # row-major: by user, items ascending
+        counts = torch.zeros(n_users, dtype=torch.int64, device=m.device)
+        counts[sorted_ids[first]] = nonzero[rows].sum(dim=1)
+        ptr = torch.zeros(n_users + 1, dtype=torch.int64, device=m.device)
+        torch.cumsum(counts, 0, out=ptr[1:])
+        got = cls(ptr.to(device), c.to(dtype=torch.int64).contiguous().to(device))
+        cls.dense_builds += 1
+        cls._dense_cache.append((key, m, got))
+        del cls._dense_cache[:-4]
+        return got
+
+    def to_dense(self, user_id_list, n_items: int) -> Tensor:
+        """The fp32 ``[n_sel, n_items]`` mask these lists stand for (host side; tests and small requests)."""
+        ptr, items = self.ptr.cpu(), self.items.cpu()
+        ids = torch.as_tensor(user_id_list).reshape(-1).long().cpu()
+        out = torch.zeros((ids.numel(), n_items), dtype=torch.float32)
+        for r, u in enumerate(ids.tolist()):
+            out[r, items[ptr[u]:ptr[u + 1]]] = 1.0
+        return out
+
+
+class PositiveLists:
+    """A ``*_pos_list_df`` of the reference (columns ``user_id_idx``, ``item_id_idx_list``; src/utils_v2.py:109-113) as a
+    device CSR over all users -- ``ptr`` int64 [n_users + 1], ``items`` int64, duplicates kept -- plus ``users``, the
+    listed users in the frame's order (int64): what ``MARK_MAPK`` intersects the recommendations with."""
+
+    def __init__(self, ptr: Tensor, items: Tensor, users: Tensor):
+        self.ptr, self.items, self.users = ptr, items, users
+
+    @classmethod
+    def from_lists(cls, user_id_idx, item_id_idx_list, n_users: int, device=None) -> "PositiveLists":
+        """From the two columns: user ids and, per user, a sequence of item indices (0-based columns of the scores)."""
+        import numpy as np
+        users = np.asarray(list(user_id_idx), dtype=np.int64).reshape(-1)
+        lists = [np.asarray(list(x), dtype=np.int64).reshape(-1) for x in item_id_idx_list]
+        if len(lists) != len(users):
+            raise ValueError(f"{len(users)} users but {len(lists)} item lists")
+        if len(users) and (users.min() < 0 or users.max() >= n_users):
+            raise ValueError(f"user ids must lie in [0, {n_users})")
+        by_user = {}
+        for u, lst in zip(users.tolist(), lists):
+            if u in by_user and not np.array_equal(by_user[u], lst):
+                raise ValueError(f"user {u} is listed twice with different item lists")
+            by_user[u] = lst
+        counts = np.zeros(n_users, dtype=np.int64)
+        for u, lst in by_user.items():
+            counts[u] = len(lst)
+        ptr = np.zeros(n_users + 1, dtype=np.int64)
+        np.cumsum(counts, out=ptr[1:])
+        order = sorted(by_user)
+        items = np.concatenate([by_user[u] for u in order]) if order else np.zeros(0, dtype=np.int64)
+        return cls.from_arrays(ptr, items, users, device)
+
+    @classmethod
+    def from_frame(cls, pos_list_df, n_users: int, device=None) -> "PositiveLists":
+        return cls.from_lists(pos_list_df["user_id_idx"], pos_list_df["item_id_idx_list"], n_users, device)
+
+    @classmethod
+    def from_arrays(cls, ptr, items, users, device=None) -> "PositiveLists":
+        """From a ready CSR (anything ``torch.as_tensor`` takes)."""
+        conv = lambda a: torch.as_tensor(a).to(dtype=torch.int64, device=device).contiguous()
+        return cls(conv(ptr), conv(items), conv(users))
+
+    def validate(self, n_users: int, n_items: Optional[int] = None, where: str = "positive lists") -> "PositiveLists":
+        """The kernels read the CSR on trust (as ``SeenLists.validate``), and every listed user needs at least one
+        positive: upstream's recall divides by the list's length.  One host sync; once per frame, not per epoch."""
+        SeenLists(self.ptr, self.items).validate(n_users, where)
+        if self.users.dtype != torch.int64 or self.users.dim() != 1:
+            raise ValueError(f"{where}: users must be a 1-D int64 tensor")
+        if self.users.numel():
+            if int(self.users.min()) < 0 or int(self.users.max()) >= n_users:
+                raise ValueError(f"{where}: user ids must lie in [0, {n_users})")
+            if bool((self.ptr[self.users + 1] == self.ptr[self.users]).any()):
+                raise ValueError(f"{where}: a listed user has an empty item list (recall would divide by zero)")
+        if n_items is not None and self.items.numel() and (int(self.items.min()) < 0 or int(self.items.max()) >= n_items):
+            raise ValueError(f"{where}: item indices must lie in [0, {n_items})")
+        return self
+
+    def to(self, device) -> "PositiveLists":
+        return PositiveLists(self.ptr.to(device), self.items.to(device), self.users.to(device))
+
 
 def mask_topk(scores: Tensor, seen, k: int) -> Tensor:
     """Indices [rows, k] (int64, on the device) of the k largest ``scores * (1 - seen)`` per row, ties by lower index
@@ -933,3 +1051,172 @@ def mask_topk(scores: Tensor, seen, k: int) -> Tensor:
                                  _native.stream_of(scores.device))
     _native.check(code, "lgc_mask_topk")
     return out
+
+
+# ----------------------------------------------------------------------------------------
+# epoch evaluation: score panels -> top-k -> hits, in bounded device memory
+# ----------------------------------------------------------------------------------------
+DEFAULT_WORKSPACE_BYTES = 64 << 20
+
+
+def panel_rows(n_items: int, workspace_bytes: int = DEFAULT_WORKSPACE_BYTES) -> int:
+    """Rows of one score panel: as many fp32 rows of ``n_items`` scores as fit the workspace, at least one."""
+    return max(1, int(workspace_bytes) // (4 * int(n_items)))
+
+
+def _check_tables(users: Tensor, items: Tensor) -> None:
+    for t, name in ((users, "users"), (items, "items")):
+        _native.require_device(t, name)
+        if t.dtype != torch.float32 or t.dim() != 2 or (t.size(1) > 1 and t.stride(1) != 1) or t.stride(0) < t.size(1):
+            raise TypeError(f"{name} must be a 2-D fp32 table with unit inner stride")
+    if users.size(1) != items.size(1) or users.device != items.device:
+        raise TypeError("users and items must have the same width and live on the same device")
+    if items.size(0) < 1:
+        raise ValueError("no items to score")
+
+
+def _check_ids(ids: Optional[Tensor], like: Tensor, name: str) -> None:
+    if ids is None:
+        return
+    if ids.dtype != torch.int64 or ids.dim() != 1 or not ids.is_contiguous() or ids.device != like.device:
+        raise TypeError(f"{name} must be a contiguous 1-D int64 tensor on the tables' device")
+
+
+def _score_panel(lib, users: Tensor, ids_ptr: Optional[int], n_rows: int, items: Tensor, out_ptr: int, out_stride: int) -> None:
+    dev = users.device
+    code = lib.lgc_score_rows(_native.ptr(users), users.stride(0), users.size(0), ids_ptr, n_rows, _native.ptr(items),
+                              items.stride(0), items.size(0), users.size(1), out_ptr, out_stride, _native.ptr(_status(dev)),
+                              _native.stream_of(dev))
+    _native.check(code, "lgc_score_rows")
+
+
+def score_rows(users: Tensor, row_ids: Optional[Tensor], items: Tensor, out: Optional[Tensor] = None) -> Tensor:
+    """``out[r, i] = <users[row_ids[r]], items[i]>`` (fp32 ``[n_rows, n_items]``; ``row_ids`` None = every user row in
+    order): lgc_score_rows.  The bits of an entry depend only on its two rows, not on where it sits or on the panel it
+    is computed in.  An id outside the table zero-fills its row and raises at ``check_index_status()``."""
+    _check_tables(users, items)
+    _check_ids(row_ids, users, "row_ids")
+    n_rows, n_items = users.size(0) if row_ids is None else row_ids.numel(), items.size(0)
+    if out is None:
+        out = torch.empty((n_rows, n_items), dtype=torch.float32, device=users.device)
+    elif (out.dtype != torch.float32 or out.shape != (n_rows, n_items) or out.device != users.device
+          or (n_items > 1 and out.stride(1) != 1) or (n_rows > 1 and out.stride(0) < n_items)):
+        raise TypeError(f"out must be fp32 [{n_rows}, {n_items}] with unit inner stride on the tables' device")
+    with torch.cuda.device(users.device):
+        _score_panel(_native.load(), users, _native.ptr(row_ids), n_rows, items, _native.ptr(out),
+                     out.stride(0) if n_rows > 1 else n_items)
+    _snapshot_status(users.device)
+    return out
+
+
+_score_workspaces = {}
+
+
+def _score_workspace(device: torch.device, n_floats: int) -> Tensor:
+    """Per (device, stream): the score panel, allocated once and reused (grown when a request needs more)."""
+    key = _scratch_key(device)[:2]
+    got = _score_workspaces.get(key)
+    if got is None or got.numel() < n_floats:
+        _score_workspaces.pop(key, None)
+        got = None                                   # let go of the old one before asking for the new one
+        got = torch.empty(n_floats, dtype=torch.float32, device=device)
+        _score_workspaces[key] = got
+    return got
+
+
+def recommend_topk(users: Tensor, sel: Tensor, items: Tensor, seen: Optional[SeenLists], k: int,
+                   workspace_bytes: int = DEFAULT_WORKSPACE_BYTES, return_values: bool = False):
+    """Indices int64 ``[n_sel, k]`` (on the device) of the k largest ``<users[sel[r]], items[i]> * (1 - seen)`` per row,
+    ties by lower index -- what ``recommendK`` ranks, without ever holding more than one panel of
+    ``panel_rows(n_items, workspace_bytes)`` score rows: per panel one lgc_score_rows and one lgc_mask_topk (list form
+    of the mask; None = no mask).  The result does not depend on the panel size, bit for bit.  With
+    ``return_values`` also the masked scores fp32 ``[n_sel, k]``."""
+    _check_tables(users, items)
+    _check_ids(sel, users, "sel")
+    n_sel, n_items, dev = sel.numel(), items.size(0), users.device
+    if k > TOPK_MAX:
+        raise ValueError(f"the list form of the mask supports k <= {TOPK_MAX}")
+    if not 1 <= k <= n_items:
+        raise RuntimeError(f"selected index k out of range: k={k}, {n_items} columns")      # torch.topk's error class
+    if seen is not None:
+        if not isinstance(seen, SeenLists):
+            raise TypeError("seen must be a SeenLists (SeenLists.from_dense converts the reference's dense mask) or None")
+        _check_ids(seen.ptr, users, "seen.ptr")
+        _check_ids(seen.items, users, "seen.items")
+    index = torch.empty((n_sel, k), dtype=torch.int64, device=dev)
+    value = torch.empty((n_sel, k), dtype=torch.float32, device=dev) if return_values else None
+    if n_sel:
+        rows = min(n_sel, panel_rows(n_items, workspace_bytes))
+        panel = _score_workspace(dev, rows * n_items)
+        lib = _native.load()
+        # lgc_mask_topk reads the lists of a row's user on trust: an id outside them is clamped for that read (its score
+        # row is zero-filled and the id reported through the index status by lgc_score_rows)
+        list_rows = sel.clamp(0, seen.ptr.numel() - 2) if seen else None
+        with torch.cuda.device(dev):
+            stream = _native.stream_of(dev)
+            for lo in range(0, n_sel, rows):
+                n = min(rows, n_sel - lo)
+                _score_panel(lib, users, sel.data_ptr() + 8 * lo, n, items, panel.data_ptr(), n_items)
+                code = lib.lgc_mask_topk(panel.data_ptr(), n_items, None, 0, _native.ptr(seen.ptr) if seen else None,
+                                         _native.ptr(seen.items) if seen else None,
+                                         list_rows.data_ptr() + 8 * lo if seen else None, n, n_items, k,
+                                         index.data_ptr() + 8 * k * lo, value.data_ptr() + 4 * k * lo if return_values else None,
+                                         stream)
+                _native.check(code, "lgc_mask_topk")
+        _snapshot_status(dev)
+    return (index, value) if return_values else index
+
+
+def topk_hits(topk: Tensor, positives: PositiveLists, users: Tensor):
+    """(hits int32 [n], recall float64 [n]) on the device: per row the number of its top-k items among the positives of
+    ``users[r]`` and that number over the list's length (lgc_topk_hits)."""
+    _native.require_device(topk, "topk")
+    if topk.dtype != torch.int64 or topk.dim() != 2 or topk.size(1) < 1 or topk.stride(1) != 1:
+        raise TypeError("topk must be a 2-D int64 tensor with unit inner stride")
+    _check_ids(users, topk, "users")
+    _check_ids(positives.ptr, topk, "positives.ptr")
+    _check_ids(positives.items, topk, "positives.items")
+    n, k, dev = topk.size(0), topk.size(1), topk.device
+    if users.numel() != n:
+        raise ValueError(f"{n} rows of recommendations for {users.numel()} users")
+    hits = torch.empty(n, dtype=torch.int32, device=dev)
+    recall = torch.empty(n, dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        code = _native.load().lgc_topk_hits(_native.ptr(topk), topk.stride(0) if n > 1 else k, k, _native.ptr(positives.ptr),
+                                            _native.ptr(positives.items), _native.ptr(users), n, positives.ptr.numel() - 1,
+                                            _native.ptr(hits), _native.ptr(recall), _native.ptr(_status(dev)),
+                                            _native.stream_of(dev))
+    _native.check(code, "lgc_topk_hits")
+    return hits, recall
+
+
+def metric_sums(hits: Tensor, recall: Tensor) -> Tensor:
+    """int64 [2] on the device: the sum of ``hits`` and the BITS of the fp64 sum of ``recall`` (``.view(torch.float64)``),
+    added in a fixed order by one workgroup (lgc_metric_sums): the same bits on every run."""
+    dev = hits.device
+    out = torch.zeros(2, dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        code = _native.load().lgc_metric_sums(_native.ptr(hits), _native.ptr(recall), hits.numel(), _native.ptr(out),
+                                              _native.ptr(out[1:]), _native.stream_of(dev))
+    _native.check(code, "lgc_metric_sums")
+    return out
+
+
+def evaluate_topk(users_table: Tensor, items: Tensor, seen: Optional[SeenLists], users: Tensor, positives: PositiveLists,
+                  k: int, workspace_bytes: int = DEFAULT_WORKSPACE_BYTES):
+    """(precision, recall, hits): MARK_MAPK's two means (src/lightgcn.py:184-190) over ``users`` as Python floats and the
+    per-user hit counts (int32, left on the device).  One host sync, at the end: two sums and the index status."""
+    top = recommend_topk(users_table, users, items, seen, k, workspace_bytes)
+    hits, recall = topk_hits(top, positives, users)
+    n, dev = users.numel(), users.device
+    if n == 0:
+        return float("nan"), float("nan"), hits                          # upstream: the mean of an empty column
+    sums = metric_sums(hits, recall)
+    host = torch.cat([sums, _status(dev)[:1].to(torch.int64)]).cpu()     # the one sync
+    if int(host[2]) & _native.ST_INDEX_OOB:
+        try:
+            check_index_status(dev)                                      # clears the word and its host snapshot
+        except IndexError:
+            pass
+        raise IndexError("evaluation: a user id lies outside the user table or the positive lists")
+    return int(host[0]) / (k * n), float(host[1:2].view(torch.float64)[0]) / n, hits

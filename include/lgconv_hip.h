@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define LGC_ABI_VERSION 13
+#define LGC_ABI_VERSION 14
 
 /* argument errors (negative return values) */
 #define LGC_E_INVAL      (-1)  /* null pointer, negative size, bad flag                    */
@@ -525,6 +525,45 @@ int lgc_pair_dot(const float *emb, int64_t stride, int32_t dim, int64_t n_nodes,
 int lgc_mask_topk(const float *scores, int64_t score_stride, const float *seen, int64_t seen_stride,
                   const int64_t *list_ptr, const int64_t *list_items, const int64_t *list_rows, int64_t n_rows,
                   int32_t n_cols, int32_t k, int64_t *out_index, float *out_value, void *stream);
+
+/* ---------------------------------------------------------------------------------------
+ * Epoch evaluation (TrainLightGCN.test, src/train_lightgcn.py:155-162: recommendK over all validation users,
+ * then MARK_MAPK): scores, ranking and metrics in bounded device memory.  A caller walks its users in panels:
+ * lgc_score_rows -> lgc_mask_topk (list form, list_rows = the panel's users) per panel, then lgc_topk_hits and
+ * lgc_metric_sums once.
+ *
+ * lgc_score_rows: out[r, i] = sum_d users[row_ids[r], d] * items[i, d], a dense fp32 panel.
+ *   users    fp32 [n_user_rows, dim], rows user_stride floats apart (>= dim; columns past dim are never read)
+ *   row_ids  int64 [n_rows], any order, repeats allowed; NULL = row r is user row r.  An id outside
+ *            [0, n_user_rows) sets LGC_ST_INDEX_OOB in `status` and zero-fills its row; nothing is read out of range
+ *   items    fp32 [n_items, dim], rows item_stride floats apart
+ *   dim      as lgc_dim_ok (LGC_E_DIM otherwise)
+ *   out      fp32 [n_rows, n_items], rows out_stride floats apart (>= n_items)
+ * The bits of out[r, i] depend only on the two source rows and dim: one chain of fused multiply-adds over d in
+ * ascending order.  They do not depend on r, i, n_rows, n_items, the strides or how a request is cut into panels. */
+int lgc_score_rows(const float *users, int64_t user_stride, int64_t n_user_rows, const int64_t *row_ids,
+                   int64_t n_rows, const float *items, int64_t item_stride, int32_t n_items, int32_t dim,
+                   float *out, int64_t out_stride, int32_t *status, void *stream);
+
+/* hits[r] = number of entries of topk[r, 0..k) that occur in the positive list of the row's user, and
+ * recall[r] = hits[r] / (pos_ptr[u + 1] - pos_ptr[u]) -- MARK_MAPK's per-user columns (src/lightgcn.py:184-190).
+ *   topk       int64 [n_rows, k], rows topk_stride apart, entries of a row distinct (lgc_mask_topk's output);
+ *              k <= 256 (LGC_E_RANGE beyond)
+ *   pos_ptr / pos_items   int64 [n_users + 1] / int64: the positive lists as a CSR.  A positive listed twice hits
+ *              once (upstream intersects sets) but counts twice in the denominator (upstream's len of the list);
+ *              an empty list gives recall NaN (upstream divides by zero)
+ *   list_rows  int64 [n_rows] = the user of each row (NULL: row r is user r), as in lgc_mask_topk; a user outside
+ *              [0, n_users) sets LGC_ST_INDEX_OOB in `status`, hits 0 and recall 0
+ *   hits int32 [n_rows], recall double [n_rows] */
+int lgc_topk_hits(const int64_t *topk, int64_t topk_stride, int32_t k, const int64_t *pos_ptr,
+                  const int64_t *pos_items, const int64_t *list_rows, int64_t n_rows, int64_t n_users,
+                  int32_t *hits, double *recall, int32_t *status, void *stream);
+
+/* *hits_sum = sum of hits[0..n_rows) (int64), *recall_sum = sum of recall[0..n_rows) (double), by one workgroup in a
+ * fixed order: the same bits on every run.  Either output (with its input) may be NULL, not both.  n_rows == 0
+ * writes nothing. */
+int lgc_metric_sums(const int32_t *hits, const double *recall, int64_t n_rows, int64_t *hits_sum,
+                    double *recall_sum, void *stream);
 
 /* ---------------------------------------------------------------------------------------
  * Mini-batch sampler: for each of the `n` given users one positive and one negative item.
