@@ -11,6 +11,7 @@ from . import _native
 from .graph import PropGraph, build_row_plan, clear_cache, get_graph
 from .lgconv import LGConv
 from .lightgcn import BPRLoss, LightGCN, regularization_loss
+from .paths import compute_paths, hop_distances, paths_frame, shortest_paths
 from .propagate import (PositiveLists, SeenLists, check_index_status, hop, pair_dot, propagate_sum, recommend_topk,
                         score_rows)
 from .sampler import TripleSampler
@@ -19,4 +20,4 @@ from .trainer import PartitionedTrainer
 
 __all__ = ["LightGCN", "BPRLoss", "LGConv", "PropGraph", "get_graph", "clear_cache", "build_row_plan",
            "propagate_sum", "hop", "pair_dot", "check_index_status", "TripleSampler", "regularization_loss", "PartitionedTrainer", "_native",
-           "SeenLists", "PositiveLists", "score_rows", "recommend_topk"]
+           "SeenLists", "PositiveLists", "score_rows", "recommend_topk", "hop_distances", "shortest_paths", "paths_frame", "compute_paths"]

@@ -146,6 +146,13 @@ SIGNATURES = {
     "lgc_topk_hits": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p,
                               c_void_p, c_void_p]),
     "lgc_metric_sums": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "lgc_bfs_init": (c_int, [c_void_p, c_int32, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "lgc_bfs_level": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int32, c_uint64, c_void_p, c_void_p,
+                              c_void_p, c_void_p, c_void_p]),
+    "lgc_bfs_resolve": (c_int, [c_void_p, c_void_p, c_int32, c_int64, c_int64, c_void_p, c_int32, c_void_p, c_void_p, c_void_p,
+                                c_void_p]),
+    "lgc_bfs_backtrack": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_int64,
+                                  c_void_p, c_int32, c_void_p]),
     "lgc_sample_triples": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_uint64,
                                    c_uint64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "lgc_pair_dot": (c_int, [c_void_p, c_int64, c_int32, c_int64, c_void_p, c_void_p, c_int64, c_void_p,
@@ -208,6 +215,8 @@ def require_device(t: torch.Tensor, name: str) -> None:
 
 
 MAX_TERMS = 8
+BFS_MAX_SOURCES = 64   # LGC_BFS_MAX_SOURCES: sources one batch of the BFS carries
+BFS_UNSET = -3         # LGC_BFS_UNSET
 SEED_MAX = 8192        # LGC_SEED_MAX: ids one lgc_seed_prepare launch sorts
 
 

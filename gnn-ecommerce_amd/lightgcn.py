@@ -7,7 +7,8 @@ src/inference_lightgcn.py and torchserve/lightgcn_handler.py run unchanged
 (``alpha``, ``embedding.weight``), and the methods ``get_embedding``, ``forward``,
 ``predict_link``, ``recommend``, ``recommendK``, ``MARK_MAPK``, ``link_pred_loss``,
 ``recommendation_loss``.  ``recommend_topk`` and ``evaluateK`` are additions: the epoch's evaluation
-(``recommendK`` over all validation users, then ``MARK_MAPK``) in bounded device memory.  What changes is underneath: propagation is the HIP CSR-SpMM with
+(``recommendK`` over all validation users, then ``MARK_MAPK``) in bounded device memory; ``recommendation_paths`` is one too: hop
+distances and shortest paths from users to their recommended items (src/inference_lightgcn.py:85-119).  What changes is underneath: propagation is the HIP CSR-SpMM with
 the layer sum fused (``propagate.propagate_sum``) and pair scoring is one gather-dot kernel.
 """
 from __future__ import annotations
@@ -22,6 +23,7 @@ from torch.nn.modules.loss import _Loss
 from . import _native
 from .graph import get_graph
 from .lgconv import LGConv
+from .paths import shortest_paths
 from .propagate import (DEFAULT_WORKSPACE_BYTES, TOPK_MAX, PositiveLists, RegHook, SeenLists, bpr_loss_fused, evaluate_topk,
                         mask_topk, pair_dot, propagate_sum, recommend_topk, regularization_through, routable_index,
                         scores_from_table)
@@ -220,6 +222,21 @@ class LightGCN(torch.nn.Module):
         if positives.ptr.device != ids.device:
             positives = positives.to(ids.device)
         return evaluate_topk(user_t, item_t, seen, ids, positives, k, workspace_bytes)
+
+    def recommendation_paths(self, edge_index, edge_weight, n_users, users, top_items, max_len: int = 7,
+                             workspace_bytes: int = DEFAULT_WORKSPACE_BYTES, trace: Optional[list] = None):
+        """``(path_lens int32 [S, k], longer_than_3 bool [S], paths int64 [S, k, max_len + 1])`` on the device: what
+        ``InferenceLightGCN.compute_paths`` (src/inference_lightgcn.py:85-119) derives per user from ``top_items`` --
+        ``recommend_topk``'s item indices, without offset -- in graph node ids (items offset by ``n_users``).  See
+        ``paths.shortest_paths``: -1 and an all -1 row for an item without a path, the distance and an all -1 row for
+        one farther than ``max_len``."""
+        normalize = self.convs[0].normalize if self.num_layers > 0 else True
+        graph = get_graph(edge_index, edge_weight, self.num_nodes, normalize)
+        ids = users if torch.is_tensor(users) else torch.as_tensor(list(users), dtype=torch.int64)
+        ids = ids.reshape(-1).to(device=graph.device, dtype=torch.int64).contiguous()
+        targets = (top_items.to(device=graph.device, dtype=torch.int64) + int(n_users)).contiguous()
+        dist, paths = shortest_paths(graph, ids, targets, max_len=max_len, workspace_bytes=workspace_bytes, trace=trace)
+        return dist, (dist > 3).any(dim=1), paths
 
     def link_pred_loss(self, pred: Tensor, edge_label: Tensor, **kwargs) -> Tensor:
         return torch.nn.BCEWithLogitsLoss(**kwargs)(pred, edge_label.to(pred.dtype))

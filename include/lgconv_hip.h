@@ -566,6 +566,55 @@ int lgc_metric_sums(const int32_t *hits, const double *recall, int64_t n_rows, i
                     double *recall_sum, void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Hop distances and shortest paths from users to their recommended items (InferenceLightGCN.compute_paths,
+ * src/inference_lightgcn.py:85-119: per pair has_path + shortest_path_length + shortest_path of networkx on the host).
+ * Here: a level-synchronous BFS from up to LGC_BFS_MAX_SOURCES sources at once over the forward CSR of lgc_build_csr
+ * (row v lists the sources j of the edges j -> v: the pull direction of the search and the predecessor list of the
+ * walk back).  Bit containers are uint64 words, one per node: bit b of seen[v] = "source b has reached v".  Entry
+ * values are ignored: an edge of weight 0 or of negative weight is an edge.  All results are integers; they are the same
+ * bits on every run (the only atomics are integer OR and integer counts).
+ *
+ * lgc_bfs_init      seen[v] = frontier[v] = 0 for v < n_nodes, then bit b set at sources[b] in both (int64 [n_sources];
+ *                   two sources may name one node: both bits are set).  A source outside [0, n_nodes) sets
+ *                   LGC_ST_INDEX_OOB in `status` and no bit.
+ * lgc_bfs_level     for every row v of [row_begin, row_end):
+ *                       fresh = (OR over the row's columns j of frontier_in[j]) & ~seen[v]
+ *                       frontier_out[v] = fresh;  seen[v] |= fresh
+ *                   by the row plan of lgc_spmm: rows of at most `short_max` entries by a lane group each, longer rows per
+ *                   chunk of `chunks` (every longer row must be listed), one wavefront each; a row cut into several chunks
+ *                   (slot >= 0) combines them with 64-bit atomic OR.  A row with (~seen[v] & active) == 0 -- `active` =
+ *                   the mask of the batch's valid source bits -- is finished without reading its entries.  active == 0
+ *                   launches nothing.  frontier_out must not be frontier_in.  The launch ADDS to `counters` (uint64 [4],
+ *                   zeroed by the caller): [0] += nodes newly reached, [2] |= their new bits, i.e. the sources whose
+ *                   frontier is not empty after this level; [1] belongs to lgc_bfs_resolve, [3] is reserved.
+ * lgc_bfs_resolve   for every pair (b, c) with dist[b, c] == LGC_BFS_UNSET (int32 [n_sources, n_targets], filled with it by
+ *                   the caller): dist = level if bit b of frontier[targets[b, c]] is set (targets int64 [n_sources,
+ *                   n_targets]).  A source or target outside [0, n_nodes): LGC_ST_INDEX_OOB, dist = -1.  counters[1] +=
+ *                   pairs settled by this call, so the caller knows how many are still unset.
+ * lgc_bfs_backtrack one shortest path per pair with 0 <= d = dist[b, c] < min(n_levels, path_len), from `levels` (uint64
+ *                   [n_levels, n_nodes]: row l = the frontier_out of level l, row 0 = lgc_bfs_init's frontier):
+ *                   paths[b, c, d] = the target, and for l = d - 1 ... 0 paths[b, c, l] = the first column, in the stored
+ *                   entry order of the row of paths[b, c, l + 1], that has bit b set in levels[l].  Positions past d, and
+ *                   the whole row of every other pair, are -1.  paths int64 [n_sources, n_targets, path_len].
+ *
+ * More than LGC_BFS_MAX_SOURCES sources, or n_nodes / n_targets that do not fit int32: LGC_E_RANGE.  No sources or no
+ * targets: nothing is launched.
+ * ------------------------------------------------------------------------------------- */
+#define LGC_BFS_MAX_SOURCES 64
+#define LGC_BFS_UNSET (-3)     /* dist of a pair no level has settled yet (-1 and -2 are results: see paths.py) */
+int lgc_bfs_init(const int64_t *sources, int32_t n_sources, int64_t n_nodes, uint64_t *seen, uint64_t *frontier,
+                 int32_t *status, void *stream);
+int lgc_bfs_level(const int32_t *rowptr, const lgc_entry *entries, int32_t row_begin, int32_t row_end, int32_t short_max,
+                  const lgc_chunk *chunks, int32_t n_chunks, uint64_t active, const uint64_t *frontier_in,
+                  uint64_t *frontier_out, uint64_t *seen, uint64_t *counters, void *stream);
+int lgc_bfs_resolve(const int64_t *sources, const int64_t *targets, int32_t n_sources, int64_t n_targets, int64_t n_nodes,
+                    const uint64_t *frontier, int32_t level, int32_t *dist, uint64_t *counters, int32_t *status,
+                    void *stream);
+int lgc_bfs_backtrack(const int32_t *rowptr, const lgc_entry *entries, int64_t n_nodes, const uint64_t *levels,
+                      int32_t n_levels, const int64_t *targets, const int32_t *dist, int32_t n_sources, int64_t n_targets,
+                      int64_t *paths, int32_t path_len, void *stream);
+
+/* ---------------------------------------------------------------------------------------
  * Mini-batch sampler: for each of the `n` given users one positive and one negative item.
  * Replaces the per-row Python of batch_loader (src/utils_v2.py:168-181; its caller
  * src/train_lightgcn.py:132): `p = random.choice(item_id_idx_list)`,
