@@ -12,12 +12,13 @@ from .graph import PropGraph, build_row_plan, clear_cache, get_graph
 from .lgconv import LGConv
 from .lightgcn import BPRLoss, LightGCN, regularization_loss
 from .paths import compute_paths, hop_distances, paths_frame, shortest_paths
-from .propagate import (PositiveLists, SeenLists, check_index_status, hop, pair_dot, propagate_sum, recommend_topk,
-                        score_rows)
+from .propagate import (PositiveLists, RankingResult, SeenLists, check_index_status, evaluate_ranking, hop, metrics_frame,
+                        overlap_items, pair_dot, propagate_sum, rank_metrics, recommend_topk, score_rows)
 from .sampler import TripleSampler
 from . import ingest, serving
 from .trainer import PartitionedTrainer
 
 __all__ = ["LightGCN", "BPRLoss", "LGConv", "PropGraph", "get_graph", "clear_cache", "build_row_plan",
            "propagate_sum", "hop", "pair_dot", "check_index_status", "TripleSampler", "regularization_loss", "PartitionedTrainer", "_native",
-           "SeenLists", "PositiveLists", "score_rows", "recommend_topk", "hop_distances", "shortest_paths", "paths_frame", "compute_paths"]
+           "SeenLists", "PositiveLists", "score_rows", "recommend_topk", "hop_distances", "shortest_paths", "paths_frame", "compute_paths",
+           "rank_metrics", "evaluate_ranking", "overlap_items", "metrics_frame", "RankingResult"]

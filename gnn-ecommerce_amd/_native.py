@@ -146,6 +146,11 @@ SIGNATURES = {
     "lgc_topk_hits": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p,
                               c_void_p, c_void_p]),
     "lgc_metric_sums": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "lgc_rank_metrics": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64,
+                                 POINTER(c_int32), c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "lgc_column_sums": (c_int, [c_void_p, c_int64, c_int64, c_int32, c_void_p, c_void_p]),
+    "lgc_topk_coverage": (c_int, [c_void_p, c_int64, c_int32, c_int64, POINTER(c_int32), c_int32, c_int64, c_void_p, c_void_p,
+                                  c_void_p, c_void_p]),
     "lgc_bfs_init": (c_int, [c_void_p, c_int32, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "lgc_bfs_level": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int32, c_uint64, c_void_p, c_void_p,
                               c_void_p, c_void_p, c_void_p]),
@@ -218,6 +223,10 @@ MAX_TERMS = 8
 BFS_MAX_SOURCES = 64   # LGC_BFS_MAX_SOURCES: sources one batch of the BFS carries
 BFS_UNSET = -3         # LGC_BFS_UNSET
 SEED_MAX = 8192        # LGC_SEED_MAX: ids one lgc_seed_prepare launch sorts
+# lgc_rank_metrics: the columns of its metrics output (LGC_RM_*), the most cutoffs of one call, lgc_column_sums' widest input
+RM_PRECISION, RM_RECALL, RM_NDCG, RM_AP, RM_RR, RM_HIT, RM_COUNT = range(7)
+RM_MAX_CUTOFFS = 8
+COLUMN_SUMS_MAX = 64
 
 
 def lincomb(y: torch.Tensor, terms) -> torch.Tensor:

@@ -553,6 +553,192 @@ __global__ __launch_bounds__(kSumBlock) void k_metric_sums(const int32_t *__rest
     }
 }
 
+// ----------------------------------------------------------------------------------------
+// Ranking metrics per row at several cutoffs, column sums, catalogue coverage
+// ----------------------------------------------------------------------------------------
+// The cutoffs and the discount table d_j = 1 / log2(j + 2) travel by value with the launch: the host computes the table
+// once, in double, and the kernel never calls log2.
+struct RankCuts {
+    int32_t n;
+    int32_t c[LGC_RM_MAX_CUTOFFS];
+};
+struct RankDiscounts {
+    double d[kTopkMax];
+};
+
+// k_topk_hits' shape -- one wavefront per row, the row's top-k in LDS, the lanes striding over the positive list and
+// flagging the entries they meet -- and then: four ballots turn the flags into the row's hit_bits words, and lane 0
+// walks the bits in ascending j with every sum a running sum, of which a cutoff is a snapshot.  The value at a cutoff c
+// is therefore the same chain of operations whatever k, n_cut and the other cutoffs are.  len = the list's length with
+// duplicates (recall's denominator), nd = its number of distinct items (what IDCG and AP can at most reach).
+__global__ __launch_bounds__(kBlock) void k_rank_metrics(const int64_t *__restrict__ topk, int64_t topk_stride, int32_t k,
+                                                        const int64_t *__restrict__ pos_ptr,
+                                                        const int64_t *__restrict__ pos_items,
+                                                        const int64_t *__restrict__ pos_distinct,
+                                                        const int64_t *__restrict__ list_rows, int64_t n_rows,
+                                                        int64_t n_users, const RankCuts cuts, const RankDiscounts disc,
+                                                        uint64_t *__restrict__ hit_bits, int32_t *__restrict__ hits,
+                                                        double *__restrict__ metrics, int32_t *__restrict__ status) {
+    __shared__ int64_t sh_top[kHitsRows][kTopkMax];
+    __shared__ int sh_flag[kHitsRows][kTopkMax];
+    const int lane = threadIdx.x & (kWave - 1), wv = threadIdx.x / kWave;
+    const int64_t r = (int64_t)blockIdx.x * kHitsRows + wv;
+    const bool live = r < n_rows;
+    int64_t u = 0;
+    bool ok = false;
+    if (live) {
+        u = list_rows ? list_rows[r] : r;
+        ok = u >= 0 && u < n_users;
+        for (int e = lane; e < k; e += kWave) {
+            sh_top[wv][e] = topk[r * topk_stride + e];
+            sh_flag[wv][e] = 0;
+        }
+    }
+    __syncthreads();
+    int64_t len = 0;
+    if (live && ok) {
+        const int64_t lo = pos_ptr[u], hi = pos_ptr[u + 1];
+        len = hi - lo;
+        for (int64_t p = lo + lane; p < hi; p += kWave) {
+            const int64_t it = pos_items[p];
+            for (int e = 0; e < k; ++e)
+                if (sh_top[wv][e] == it) sh_flag[wv][e] = 1;
+        }
+    }
+    __syncthreads();
+    if (!live) return;                                       // whole wavefronts: no barrier follows
+    unsigned long long word[kTopkMax / kWave];
+#pragma unroll
+    for (int q = 0; q < kTopkMax / kWave; ++q) {
+        const int e = q * kWave + lane;
+        word[q] = __ballot(ok && e < k && sh_flag[wv][e] != 0);   // entries past k are no bits
+    }
+    if (lane != 0) return;
+    if (!ok) atomicOr(status, LGC_ST_INDEX_OOB);
+    if (hit_bits) {
+#pragma unroll
+        for (int q = 0; q < kTopkMax / kWave; ++q) hit_bits[r * (kTopkMax / kWave) + q] = word[q];
+    }
+    int32_t *hrow = hits + r * cuts.n;
+    double *mrow = metrics + r * cuts.n * LGC_RM_COUNT;
+    if (!ok) {
+        for (int ci = 0; ci < cuts.n; ++ci) {
+            hrow[ci] = 0;
+            for (int m = 0; m < LGC_RM_COUNT; ++m) mrow[ci * LGC_RM_COUNT + m] = 0.0;
+        }
+        return;
+    }
+    const int64_t nd = pos_distinct ? pos_distinct[u] : len;
+    int h = 0, ci = 0;
+    double dcg = 0.0, idcg = 0.0, ap = 0.0, rr = 0.0;
+#pragma unroll
+    for (int q = 0; q < kTopkMax / kWave; ++q) {
+        const unsigned long long w = word[q];
+        for (int jj = 0; jj < kWave && ci < cuts.n; ++jj) {
+            const int j = q * kWave + jj;                    // j < the last cutoff <= k while ci < cuts.n
+            const double dj = disc.d[j];
+            if ((w >> jj) & 1ull) {
+                ++h;
+                dcg += dj;
+                ap += (double)h / (double)(j + 1);
+                if (h == 1) rr = 1.0 / (double)(j + 1);
+            }
+            if (j < nd) idcg += dj;
+            if (j + 1 == cuts.c[ci]) {
+                const int c = j + 1;
+                double *m = mrow + ci * LGC_RM_COUNT;
+                hrow[ci] = h;
+                m[LGC_RM_PRECISION] = (double)h / (double)c;
+                m[LGC_RM_RECALL] = (double)h / (double)len;
+                m[LGC_RM_NDCG] = dcg / idcg;
+                m[LGC_RM_AP] = ap / (double)(c < nd ? (int64_t)c : nd);
+                m[LGC_RM_RR] = rr;
+                m[LGC_RM_HIT] = h > 0 ? 1.0 : 0.0;
+                ++ci;
+            }
+        }
+    }
+}
+
+// out[c] = sum over r of in[r, c]: one workgroup per column, each adding in k_metric_sums' order (thread t adds rows
+// t, t + 1024, ... in that order, then the binary tree over the threads).  No atomics.
+__global__ __launch_bounds__(kSumBlock) void k_column_sums(const double *__restrict__ in, int64_t in_stride, int64_t n_rows,
+                                                          double *__restrict__ out) {
+    __shared__ double sh_c[kSumBlock];
+    const int tid = threadIdx.x;
+    const double *col = in + blockIdx.x;
+    double s = 0.0;
+    for (int64_t i = tid; i < n_rows; i += kSumBlock) s += col[i * in_stride];
+    sh_c[tid] = s;
+    __syncthreads();
+    for (int half = kSumBlock / 2; half > 0; half >>= 1) {
+        if (tid < half) sh_c[tid] += sh_c[tid + half];
+        __syncthreads();
+    }
+    if (tid == 0) out[blockIdx.x] = sh_c[0];
+}
+
+// bitmap[ci, item] |= 1 for every item among the first cuts.c[ci] entries of every row: one thread per (row, j) with
+// j below the last cutoff; integer atomic OR.  An entry is range-checked before anything is addressed with it.
+__global__ __launch_bounds__(kBlock) void k_coverage_mark(const int64_t *__restrict__ topk, int64_t topk_stride,
+                                                         int64_t n_rows, const RankCuts cuts, int64_t n_items,
+                                                         int64_t words, uint32_t *__restrict__ bitmap,
+                                                         int32_t *__restrict__ status) {
+    const int64_t width = cuts.c[cuts.n - 1], total = n_rows * width;
+    for (int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x; t < total; t += (int64_t)gridDim.x * kBlock) {
+        const int64_t r = t / width;
+        const int j = (int)(t - r * width);
+        const int64_t it = topk[r * topk_stride + j];
+        if (it < 0 || it >= n_items) {
+            atomicOr(status, LGC_ST_INDEX_OOB);
+            continue;
+        }
+        for (int ci = 0; ci < cuts.n; ++ci)
+            if (j < cuts.c[ci]) atomicOr(&bitmap[ci * words + (it >> 5)], 1u << (it & 31));
+    }
+}
+
+// counts[ci] = set bits of bitmap row ci: one workgroup per cutoff, integer sums in a fixed order.
+__global__ __launch_bounds__(kSumBlock) void k_coverage_count(const uint32_t *__restrict__ bitmap, int64_t words,
+                                                             int64_t *__restrict__ counts) {
+    __shared__ int64_t sh_n[kSumBlock];
+    const int tid = threadIdx.x;
+    const uint32_t *row = bitmap + (int64_t)blockIdx.x * words;
+    int64_t n = 0;
+    for (int64_t i = tid; i < words; i += kSumBlock) n += __popc(row[i]);
+    sh_n[tid] = n;
+    __syncthreads();
+    for (int half = kSumBlock / 2; half > 0; half >>= 1) {
+        if (tid < half) sh_n[tid] += sh_n[tid + half];
+        __syncthreads();
+    }
+    if (tid == 0) counts[blockIdx.x] = sh_n[0];
+}
+
+// The cutoffs of lgc_rank_metrics / lgc_topk_coverage: 1..8 of them, each >= 1, strictly ascending, the last <= k.
+int take_cutoffs(const int32_t *cutoffs, int32_t n_cut, int32_t k, RankCuts *out) {
+    if (!cutoffs || n_cut < 1 || n_cut > LGC_RM_MAX_CUTOFFS || k < 1) return LGC_E_INVAL;
+    if (k > kTopkMax) return LGC_E_RANGE;
+    for (int i = 0; i < n_cut; ++i) {
+        if (cutoffs[i] > kTopkMax) return LGC_E_RANGE;
+        if (cutoffs[i] < 1 || (i > 0 && cutoffs[i] <= cutoffs[i - 1])) return LGC_E_INVAL;
+    }
+    if (cutoffs[n_cut - 1] > k) return LGC_E_INVAL;
+    *out = RankCuts{};
+    out->n = n_cut;
+    for (int i = 0; i < n_cut; ++i) out->c[i] = cutoffs[i];
+    return 0;
+}
+
+const RankDiscounts &rank_discounts() {
+    static const RankDiscounts table = [] {
+        RankDiscounts t;
+        for (int j = 0; j < kTopkMax; ++j) t.d[j] = 1.0 / std::log2((double)(j + 2));
+        return t;
+    }();
+    return table;
+}
+
 }  // namespace
 
 extern "C" {
@@ -639,6 +825,52 @@ int lgc_metric_sums(const int32_t *hits, const double *recall, int64_t n_rows, i
     if (n_rows == 0) return 0;                             // nothing to add: the sums are left as they are
     hipLaunchKernelGGL(k_metric_sums, dim3(1), dim3(kSumBlock), 0, as_stream(stream_), hits_sum ? hits : nullptr,
                        recall_sum ? recall : nullptr, n_rows, hits_sum, recall_sum);
+    return (int)hipGetLastError();
+}
+
+int lgc_rank_metrics(const int64_t *topk, int64_t topk_stride, int32_t k, const int64_t *pos_ptr, const int64_t *pos_items,
+                     const int64_t *pos_distinct, const int64_t *list_rows, int64_t n_rows, int64_t n_users,
+                     const int32_t *cutoffs, int32_t n_cut, uint64_t *hit_bits, int32_t *hits, double *metrics,
+                     int32_t *status, void *stream_) {
+    if (!topk || !pos_ptr || !hits || !metrics || !status || n_rows < 0 || n_users < 0 || k < 1 || topk_stride < k)
+        return LGC_E_INVAL;
+    RankCuts cuts;
+    const int rc = take_cutoffs(cutoffs, n_cut, k, &cuts);
+    if (rc != 0) return rc;
+    if (n_rows >= INT32_MAX) return LGC_E_RANGE;
+    if (n_rows == 0) return 0;
+    hipLaunchKernelGGL(k_rank_metrics, dim3(ceil_div(n_rows, kHitsRows)), dim3(kBlock), 0, as_stream(stream_), topk,
+                       topk_stride, k, pos_ptr, pos_items, pos_distinct, list_rows, n_rows, n_users, cuts, rank_discounts(),
+                       hit_bits, hits, metrics, status);
+    return (int)hipGetLastError();
+}
+
+int lgc_column_sums(const double *in, int64_t in_stride, int64_t n_rows, int32_t n_cols, double *out, void *stream_) {
+    if (!out || n_rows < 0 || n_cols < 1 || in_stride < n_cols || (n_rows > 0 && !in)) return LGC_E_INVAL;
+    if (n_cols > LGC_COLUMN_SUMS_MAX) return LGC_E_RANGE;
+    if (n_rows == 0) return 0;                             // nothing to add: the sums are left as they are
+    hipLaunchKernelGGL(k_column_sums, dim3((unsigned)n_cols), dim3(kSumBlock), 0, as_stream(stream_), in, in_stride, n_rows,
+                       out);
+    return (int)hipGetLastError();
+}
+
+int lgc_topk_coverage(const int64_t *topk, int64_t topk_stride, int32_t k, int64_t n_rows, const int32_t *cutoffs,
+                      int32_t n_cut, int64_t n_items, uint32_t *bitmap, int64_t *counts, int32_t *status, void *stream_) {
+    if (!bitmap || !counts || !status || n_rows < 0 || n_items < 1 || k < 1 || topk_stride < k || (n_rows > 0 && !topk))
+        return LGC_E_INVAL;
+    RankCuts cuts;
+    const int rc = take_cutoffs(cutoffs, n_cut, k, &cuts);
+    if (rc != 0) return rc;
+    if (n_rows >= INT32_MAX || n_items >= INT32_MAX) return LGC_E_RANGE;
+    const int64_t words = (n_items + 31) / 32;
+    if (n_rows > 0) {
+        const int64_t blocks = std::min<int64_t>(ceil_div(n_rows * cuts.c[cuts.n - 1], kBlock), 65536);
+        hipLaunchKernelGGL(k_coverage_mark, dim3((unsigned)blocks), dim3(kBlock), 0, as_stream(stream_), topk, topk_stride,
+                           n_rows, cuts, n_items, words, bitmap, status);
+        const int rc_mark = (int)hipGetLastError();
+        if (rc_mark != 0) return rc_mark;
+    }
+    hipLaunchKernelGGL(k_coverage_count, dim3((unsigned)cuts.n), dim3(kSumBlock), 0, as_stream(stream_), bitmap, words, counts);
     return (int)hipGetLastError();
 }
 

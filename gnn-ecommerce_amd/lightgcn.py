@@ -7,7 +7,8 @@ src/inference_lightgcn.py and torchserve/lightgcn_handler.py run unchanged
 (``alpha``, ``embedding.weight``), and the methods ``get_embedding``, ``forward``,
 ``predict_link``, ``recommend``, ``recommendK``, ``MARK_MAPK``, ``link_pred_loss``,
 ``recommendation_loss``.  ``recommend_topk`` and ``evaluateK`` are additions: the epoch's evaluation
-(``recommendK`` over all validation users, then ``MARK_MAPK``) in bounded device memory; ``recommendation_paths`` is one too: hop
+(``recommendK`` over all validation users, then ``MARK_MAPK``) in bounded device memory; ``evaluate_metrics`` adds NDCG, MAP, MRR,
+hit rate and coverage at several cutoffs from the same single ranking pass; ``recommendation_paths`` is one too: hop
 distances and shortest paths from users to their recommended items (src/inference_lightgcn.py:85-119).  What changes is underneath: propagation is the HIP CSR-SpMM with
 the layer sum fused (``propagate.propagate_sum``) and pair scoring is one gather-dot kernel.
 """
@@ -24,9 +25,9 @@ from . import _native
 from .graph import get_graph
 from .lgconv import LGConv
 from .paths import shortest_paths
-from .propagate import (DEFAULT_WORKSPACE_BYTES, TOPK_MAX, PositiveLists, RegHook, SeenLists, bpr_loss_fused, evaluate_topk,
-                        mask_topk, pair_dot, propagate_sum, recommend_topk, regularization_through, routable_index,
-                        scores_from_table)
+from .propagate import (DEFAULT_WORKSPACE_BYTES, TOPK_MAX, PositiveLists, RegHook, SeenLists, bpr_loss_fused, evaluate_ranking,
+                        evaluate_topk, mask_topk, pair_dot, propagate_sum, recommend_topk, regularization_through,
+                        routable_index, scores_from_table)
 
 __all__ = ["LightGCN", "BPRLoss", "LGConv", "regularization_loss"]
 
@@ -222,6 +223,21 @@ class LightGCN(torch.nn.Module):
         if positives.ptr.device != ids.device:
             positives = positives.to(ids.device)
         return evaluate_topk(user_t, item_t, seen, ids, positives, k, workspace_bytes)
+
+    def evaluate_metrics(self, edge_index, edge_weight, n_users, n_items, seen, users, positives, ks=(5, 10, 20),
+                         workspace_bytes: int = DEFAULT_WORKSPACE_BYTES, coverage: bool = True):
+        """Precision, recall, NDCG, MAP, MRR, hit rate and catalogue coverage at every cutoff of ``ks`` (ascending) from
+        ONE ranking pass at ``max(ks)``; arguments as ``evaluateK``.  Returns a ``propagate.RankingResult``: ``mean``
+        (a dict of tuples, one Python float per cutoff) and the per-user device tensors ``topk``, ``hits``, ``metrics``
+        and ``hit_bits``.  Precision and recall at a cutoff are ``evaluateK``'s floats at that k.  One host sync."""
+        if not isinstance(positives, PositiveLists):
+            positives = PositiveLists.from_frame(positives, n_users)
+        if users is None:
+            users = positives.users
+        user_t, item_t, seen, ids = self._eval_tables(edge_index, edge_weight, n_users, n_items, seen, users)
+        if positives.ptr.device != ids.device:
+            positives = positives.to(ids.device)
+        return evaluate_ranking(user_t, item_t, seen, ids, positives, ks, workspace_bytes, coverage)
 
     def recommendation_paths(self, edge_index, edge_weight, n_users, users, top_items, max_len: int = 7,
                              workspace_bytes: int = DEFAULT_WORKSPACE_BYTES, trace: Optional[list] = None):

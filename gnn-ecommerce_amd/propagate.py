@@ -972,6 +972,25 @@ class PositiveLists:
 
     def __init__(self, ptr: Tensor, items: Tensor, users: Tensor):
         self.ptr, self.items, self.users = ptr, items, users
+        self._distinct: Optional[Tensor] = None
+
+    @property
+    def distinct(self) -> Tensor:
+        """int64 [n_users]: the number of DISTINCT items of each user's list (0 for a user without one) -- what NDCG's
+        ideal ranking and AP's denominator can at most reach, where recall divides by the length with duplicates.
+        Computed once, on the lists' device (two stable sorts order the entries by (user, item); a run's head counts),
+        and kept."""
+        if self._distinct is None:
+            dev, n_users = self.ptr.device, self.ptr.numel() - 1
+            owner = torch.repeat_interleave(torch.arange(n_users, device=dev), self.ptr[1:] - self.ptr[:-1],
+                                            output_size=self.items.numel())
+            items, order = torch.sort(self.items, stable=True)
+            owner, order = torch.sort(owner[order], stable=True)
+            items = items[order]
+            head = torch.ones_like(items, dtype=torch.bool)
+            head[1:] = (owner[1:] != owner[:-1]) | (items[1:] != items[:-1])
+            self._distinct = torch.bincount(owner[head], minlength=n_users).to(torch.int64).contiguous()
+        return self._distinct
 
     @classmethod
     def from_lists(cls, user_id_idx, item_id_idx_list, n_users: int, device=None) -> "PositiveLists":
@@ -1023,7 +1042,10 @@ class PositiveLists:
         return self
 
     def to(self, device) -> "PositiveLists":
-        return PositiveLists(self.ptr.to(device), self.items.to(device), self.users.to(device))
+        moved = PositiveLists(self.ptr.to(device), self.items.to(device), self.users.to(device))
+        if self._distinct is not None:
+            moved._distinct = self._distinct.to(device)
+        return moved
 
 
 def mask_topk(scores: Tensor, seen, k: int) -> Tensor:
@@ -1220,3 +1242,187 @@ def evaluate_topk(users_table: Tensor, items: Tensor, seen: Optional[SeenLists],
             pass
         raise IndexError("evaluation: a user id lies outside the user table or the positive lists")
     return int(host[0]) / (k * n), float(host[1:2].view(torch.float64)[0]) / n, hits
+
+
+# ----------------------------------------------------------------------------------------
+# ranking metrics at several cutoffs from one ranking pass
+# ----------------------------------------------------------------------------------------
+METRIC_NAMES = ("precision", "recall", "ndcg", "map", "mrr", "hit_rate")      # the LGC_RM_* columns, in order
+
+
+def _host_cutoffs(cutoffs, k: int):
+    """(list of ints, ctypes int32 array): 1..8 cutoffs, each >= 1, strictly ascending, the last <= k."""
+    import ctypes
+    cuts = [int(c) for c in cutoffs]
+    if not 1 <= len(cuts) <= _native.RM_MAX_CUTOFFS:
+        raise ValueError(f"1..{_native.RM_MAX_CUTOFFS} cutoffs, got {len(cuts)}")
+    if cuts[0] < 1 or any(b <= a for a, b in zip(cuts, cuts[1:])):
+        raise ValueError(f"cutoffs must be >= 1 and strictly ascending, got {cuts}")
+    if cuts[-1] > k:
+        raise ValueError(f"the largest cutoff {cuts[-1]} exceeds k = {k}")
+    return cuts, (ctypes.c_int32 * len(cuts))(*cuts)
+
+
+def _check_topk(topk: Tensor) -> None:
+    _native.require_device(topk, "topk")
+    if topk.dtype != torch.int64 or topk.dim() != 2 or topk.size(1) < 1 or topk.stride(1) != 1:
+        raise TypeError("topk must be a 2-D int64 tensor with unit inner stride")
+    if topk.size(1) > TOPK_MAX:
+        raise ValueError(f"k <= {TOPK_MAX}")
+
+
+def rank_metrics(topk: Tensor, positives: PositiveLists, users: Tensor, cutoffs, return_bits: bool = False):
+    """(hits int32 [n, C], metrics float64 [n, C, 6]) on the device, per row and per cutoff c of ``cutoffs`` (ascending,
+    the last <= topk.size(1)): the hits among the first c entries and precision, recall, NDCG, AP, RR and hit
+    (``METRIC_NAMES``; include/lgconv_hip.h: lgc_rank_metrics) against the positives of ``users[r]``.  The rows of
+    ``topk`` must be ranked and distinct (``recommend_topk``'s are).  With ``return_bits`` also ``hit_bits`` [n, 4]:
+    bit j of a row = topk[r, j] is a positive (uint64 words, held in an int64 tensor)."""
+    _check_topk(topk)
+    _check_ids(users, topk, "users")
+    _check_ids(positives.ptr, topk, "positives.ptr")
+    _check_ids(positives.items, topk, "positives.items")
+    n, k, dev = topk.size(0), topk.size(1), topk.device
+    if users.numel() != n:
+        raise ValueError(f"{n} rows of recommendations for {users.numel()} users")
+    cuts, cuts_c = _host_cutoffs(cutoffs, k)
+    hits = torch.empty((n, len(cuts)), dtype=torch.int32, device=dev)
+    metrics = torch.empty((n, len(cuts), _native.RM_COUNT), dtype=torch.float64, device=dev)
+    bits = torch.empty((n, TOPK_MAX // 64), dtype=torch.int64, device=dev) if return_bits else None
+    if n == 0:                                       # empty tensors have no address to hand over; nothing to compute
+        return (hits, metrics, bits) if return_bits else (hits, metrics)
+    distinct = positives.distinct
+    with torch.cuda.device(dev):
+        code = _native.load().lgc_rank_metrics(_native.ptr(topk), topk.stride(0) if n > 1 else k, k, _native.ptr(positives.ptr),
+                                               _native.ptr(positives.items), _native.ptr(distinct), _native.ptr(users), n,
+                                               positives.ptr.numel() - 1, cuts_c, len(cuts), _native.ptr(bits),
+                                               _native.ptr(hits), _native.ptr(metrics), _native.ptr(_status(dev)),
+                                               _native.stream_of(dev))
+    _native.check(code, "lgc_rank_metrics")
+    return (hits, metrics, bits) if return_bits else (hits, metrics)
+
+
+def column_sums(table: Tensor) -> Tensor:
+    """float64 [n_cols] on the device: the sum of every column of a 2-D float64 tensor (at most 64 columns, unit inner
+    stride), each added in ``metric_sums``' fixed order (lgc_column_sums): the same bits on every run.  No rows: zeros."""
+    _native.require_device(table, "table")
+    if table.dtype != torch.float64 or table.dim() != 2 or table.size(1) < 1 or (table.size(1) > 1 and table.stride(1) != 1):
+        raise TypeError("column_sums takes a 2-D float64 tensor with unit inner stride")
+    n, cols, dev = table.size(0), table.size(1), table.device
+    if cols > _native.COLUMN_SUMS_MAX:
+        raise ValueError(f"at most {_native.COLUMN_SUMS_MAX} columns")
+    out = torch.zeros(cols, dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        code = _native.load().lgc_column_sums(_native.ptr(table), table.stride(0) if n > 1 else cols, n, cols, _native.ptr(out),
+                                              _native.stream_of(dev))
+    _native.check(code, "lgc_column_sums")
+    return out
+
+
+def topk_coverage(topk: Tensor, cutoffs, n_items: int, bitmap: Optional[Tensor] = None):
+    """(counts int64 [C], bitmap int32 [C, ceil(n_items / 32)]) on the device: per cutoff c the number of distinct items
+    among the first c entries of all rows seen so far (lgc_topk_coverage).  Pass the returned ``bitmap`` to the next
+    call to accumulate over requests; None starts from an empty catalogue.  An entry outside [0, n_items) marks nothing
+    and raises at ``check_index_status()``."""
+    _check_topk(topk)
+    n, k, dev = topk.size(0), topk.size(1), topk.device
+    cuts, cuts_c = _host_cutoffs(cutoffs, k)
+    words = (int(n_items) + 31) // 32
+    if n_items < 1:
+        raise ValueError("no items to cover")
+    if bitmap is None:
+        bitmap = torch.zeros((len(cuts), words), dtype=torch.int32, device=dev)
+    elif bitmap.dtype != torch.int32 or bitmap.shape != (len(cuts), words) or not bitmap.is_contiguous() or bitmap.device != dev:
+        raise TypeError(f"bitmap must be a contiguous int32 [{len(cuts)}, {words}] tensor on {dev}")
+    counts = torch.empty(len(cuts), dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        code = _native.load().lgc_topk_coverage(_native.ptr(topk), topk.stride(0) if n > 1 else k, k, n, cuts_c, len(cuts),
+                                                int(n_items), _native.ptr(bitmap), _native.ptr(counts),
+                                                _native.ptr(_status(dev)), _native.stream_of(dev))
+    _native.check(code, "lgc_topk_coverage")
+    return counts, bitmap
+
+
+class RankingResult:
+    """What ``evaluate_ranking`` returns.  ``cutoffs``: the tuple of cutoffs; ``mean``: a dict from ``"precision"``,
+    ``"recall"``, ``"ndcg"``, ``"map"``, ``"mrr"``, ``"hit_rate"``, ``"coverage"`` to a tuple with one Python float per
+    cutoff (coverage = distinct recommended items / n_items); and, left on the device, ``users`` int64 [n], ``topk``
+    int64 [n, max(cutoffs)], ``hits`` int32 [n, C], ``metrics`` float64 [n, C, 6] (``METRIC_NAMES``) and ``hit_bits``
+    [n, 4] (see ``rank_metrics``)."""
+
+    def __init__(self, cutoffs, mean, users, topk, hits, metrics, hit_bits):
+        self.cutoffs, self.mean, self.users = tuple(cutoffs), mean, users
+        self.topk, self.hits, self.metrics, self.hit_bits = topk, hits, metrics, hit_bits
+
+    def __repr__(self) -> str:
+        return f"RankingResult(cutoffs={self.cutoffs}, mean={self.mean})"
+
+
+def evaluate_ranking(users_table: Tensor, items: Tensor, seen: Optional[SeenLists], users: Tensor, positives: PositiveLists,
+                     cutoffs, workspace_bytes: int = DEFAULT_WORKSPACE_BYTES, coverage: bool = True) -> RankingResult:
+    """Precision, recall, NDCG, MAP, MRR, hit rate and catalogue coverage at every cutoff from ONE ranking pass at
+    k = max(cutoffs): ``recommend_topk``, then lgc_rank_metrics, lgc_column_sums and (``coverage``) lgc_topk_coverage.
+    The first c entries of a ranked row are its top-c row, so a smaller cutoff costs no second pass.  One host sync, at
+    the end: the sums, the counts and the index status.  Precision and recall at a cutoff are the floats
+    ``evaluate_topk(k=cutoff)`` returns.  Without users the means are NaN; without ``coverage`` that entry is NaN."""
+    cuts = [int(c) for c in cutoffs]
+    _host_cutoffs(cuts, TOPK_MAX)
+    n, dev, n_items, n_cut = users.numel(), users.device, items.size(0), len(cuts)
+    top = recommend_topk(users_table, users, items, seen, cuts[-1], workspace_bytes)
+    hits, metrics, bits = rank_metrics(top, positives, users, cuts, return_bits=True)
+    nan = tuple(float("nan") for _ in cuts)
+    if n == 0:
+        mean = {name: nan for name in METRIC_NAMES}
+        mean["coverage"] = tuple(0.0 for _ in cuts) if coverage else nan
+        return RankingResult(cuts, mean, users, top, hits, metrics, bits)
+    # the hit counts ride along as exact doubles: precision's mean is then the integer sum over c * n, as evaluate_topk's
+    sums = column_sums(torch.cat([metrics.view(n, n_cut * _native.RM_COUNT), hits.to(torch.float64)], dim=1))
+    parts = [sums.view(torch.int64), _status(dev)[:1].to(torch.int64)]
+    if coverage:
+        parts.append(topk_coverage(top, cuts, n_items)[0])
+    host = torch.cat(parts).cpu()                                        # the one sync
+    width = n_cut * (_native.RM_COUNT + 1)
+    if int(host[width]) & _native.ST_INDEX_OOB:
+        try:
+            check_index_status(dev)                                      # clears the word and its host snapshot
+        except IndexError:
+            pass
+        raise IndexError("evaluation: a user id lies outside the user table or the positive lists")
+    total = host[:width].view(torch.float64).tolist()
+    mean = {name: tuple(total[ci * _native.RM_COUNT + m] / n for ci in range(n_cut)) for m, name in enumerate(METRIC_NAMES)}
+    mean["precision"] = tuple(int(total[n_cut * _native.RM_COUNT + ci]) / (c * n) for ci, c in enumerate(cuts))
+    mean["coverage"] = tuple(int(v) / n_items for v in host[width + 1:].tolist()) if coverage else nan
+    return RankingResult(cuts, mean, users, top, hits, metrics, bits)
+
+
+def overlap_items(topk: Tensor, hit_bits: Tensor, cutoff: Optional[int] = None) -> list:
+    """Per row the entries of ``topk[r, :cutoff]`` whose bit is set in ``hit_bits``, in the ranking's order, as a Python
+    list of lists: what upstream's ``list(set(a).intersection(b))`` holds.  One copy to the host."""
+    import numpy as np
+    n, k = topk.size(0), topk.size(1) if cutoff is None else int(cutoff)
+    if hit_bits.shape != (n, TOPK_MAX // 64) or hit_bits.dtype != torch.int64 or not 1 <= k <= topk.size(1):
+        raise ValueError(f"hit_bits must be int64 [{n}, {TOPK_MAX // 64}] and 1 <= cutoff <= {topk.size(1)}")
+    host = torch.cat([topk[:, :k], hit_bits.to(topk.device)], dim=1).cpu().numpy()   # the one copy
+    top, words = host[:, :k], np.ascontiguousarray(host[:, k:])
+    flags = np.unpackbits(words.view(np.uint8), axis=1, bitorder="little")[:, :k].astype(bool)
+    return [row[f].tolist() for row, f in zip(top, flags)]
+
+
+def metrics_frame(pos_list_df, result: RankingResult, cutoff: Optional[int] = None):
+    """The frame ``MARK_MAPK`` returns as its third value (src/lightgcn.py:184-190) at one cutoff of ``result`` (default:
+    the largest): ``pos_list_df`` left-merged on ``user_id_idx`` with the columns ``user_ID``, ``top_rlvnt_itm`` (the
+    first ``cutoff`` entries of the ranking), ``overlap_item``, ``recall`` and ``precision`` -- the same columns, dtypes
+    and values, built from ``result.topk``, ``result.hit_bits`` and the two metric columns instead of a per-user set
+    intersection.  ``overlap_item`` holds the same items as upstream's, in the RANKING's order: upstream's order is
+    whatever iterating a Python ``set`` gives, which nothing should rely on."""
+    import pandas as pd
+    cutoff = result.cutoffs[-1] if cutoff is None else int(cutoff)
+    if cutoff not in result.cutoffs:
+        raise ValueError(f"cutoff {cutoff} is not one of {result.cutoffs}")
+    ci = result.cutoffs.index(cutoff)
+    cols = result.metrics[:, ci, [_native.RM_RECALL, _native.RM_PRECISION]].cpu().numpy()
+    per_row = pd.DataFrame({"user_ID": result.users.cpu().numpy(),
+                            "top_rlvnt_itm": result.topk[:, :cutoff].cpu().numpy().tolist(),
+                            "overlap_item": overlap_items(result.topk, result.hit_bits, cutoff),
+                            "recall": cols[:, 0], "precision": cols[:, 1]})
+    per_row = per_row.drop_duplicates("user_ID", ignore_index=True)      # a user evaluated twice has two equal rows
+    return pd.merge(pos_list_df, per_row, how="left", left_on="user_id_idx", right_on="user_ID")

@@ -565,6 +565,63 @@ int lgc_topk_hits(const int64_t *topk, int64_t topk_stride, int32_t k, const int
 int lgc_metric_sums(const int32_t *hits, const double *recall, int64_t n_rows, int64_t *hits_sum,
                     double *recall_sum, void *stream);
 
+/* Ranking metrics per row at several cutoffs from ONE ranking: the rows of lgc_mask_topk are sorted by (value descending,
+ * index ascending), so the first c entries of a top-k row are the top-c row.  Stands in for MARK_MAPK's per-user columns
+ * (src/lightgcn.py:184-190: overlap_item, recall, precision) and adds what its name promises and it does not compute.
+ *   topk, topk_stride, k, pos_ptr, pos_items, list_rows, n_rows, n_users, status   as lgc_topk_hits (entries of a row
+ *              distinct; a user outside [0, n_users) sets LGC_ST_INDEX_OOB and every output of its row is 0)
+ *   pos_distinct  int64 [n_users]: the number of DISTINCT items of each user's list (n below); NULL = the lists hold no
+ *              duplicates and the list length is used.  len = pos_ptr[u + 1] - pos_ptr[u] counts duplicates
+ *   cutoffs    int32 [n_cut] on the HOST, 1 <= n_cut <= LGC_RM_MAX_CUTOFFS, each >= 1, strictly ascending, the last <= k
+ *              (LGC_E_INVAL otherwise; k or a cutoff above 256: LGC_E_RANGE)
+ *   hit_bits   uint64 [n_rows, 4] or NULL: bit j of the row (bit j % 64 of word j / 64) is set when topk[r, j] occurs in
+ *              the user's list; bits at and past k are zero.  rel_j below is bit j
+ *   hits       int32 [n_rows, n_cut]: hits@c = the number of set bits below c
+ *   metrics    double [n_rows, n_cut, LGC_RM_COUNT], per cutoff c:
+ *     LGC_RM_PRECISION  hits@c / c
+ *     LGC_RM_RECALL     hits@c / len                 (at c == k the bits of lgc_topk_hits' recall)
+ *     LGC_RM_NDCG       DCG@c / IDCG@c,  DCG@c = sum_{j<c} rel_j d_j,  IDCG@c = sum_{j<min(c,n)} d_j,  d_j = 1 / log2(j + 2)
+ *     LGC_RM_AP         (sum_{j<c} rel_j hits@(j+1) / (j+1)) / min(c, n)
+ *     LGC_RM_RR         1 / (j0 + 1) for the lowest set bit j0 < c, else 0
+ *     LGC_RM_HIT        1.0 if hits@c > 0, else 0.0
+ * All arithmetic is double; d_j is a table the host computes once.  Every sum over j is a running sum in ascending j and a
+ * cutoff is a snapshot of it: the value at cutoff c does not depend on k, n_cut or the other cutoffs, bit for bit.  An
+ * empty list gives NaN in recall, NDCG and AP (0 / 0, as upstream's division).  No float atomics: the same bits on
+ * every run.  Nothing is read through a topk entry; entries are only compared. */
+#define LGC_RM_PRECISION 0
+#define LGC_RM_RECALL    1
+#define LGC_RM_NDCG      2
+#define LGC_RM_AP        3
+#define LGC_RM_RR        4
+#define LGC_RM_HIT       5
+#define LGC_RM_COUNT     6
+#define LGC_RM_MAX_CUTOFFS 8
+int lgc_rank_metrics(const int64_t *topk, int64_t topk_stride, int32_t k, const int64_t *pos_ptr,
+                     const int64_t *pos_items, const int64_t *pos_distinct, const int64_t *list_rows, int64_t n_rows,
+                     int64_t n_users, const int32_t *cutoffs, int32_t n_cut, uint64_t *hit_bits, int32_t *hits,
+                     double *metrics, int32_t *status, void *stream);
+
+/* out[c] = sum over r of in[r, c] for a double [n_rows, n_cols] matrix, rows in_stride doubles apart: the means of
+ * MARK_MAPK (src/lightgcn.py:184-190, the two .mean() calls) for every metric column at once.  Per column the additions
+ * run in lgc_metric_sums' order (thread t adds rows t, t + 1024, ..., then a binary tree), so the sum of a recall column
+ * has the bits of lgc_metric_sums' recall_sum.  n_cols <= LGC_COLUMN_SUMS_MAX (LGC_E_RANGE beyond).  No atomics.
+ * n_rows == 0 writes nothing. */
+#define LGC_COLUMN_SUMS_MAX 64
+int lgc_column_sums(const double *in, int64_t in_stride, int64_t n_rows, int32_t n_cols, double *out, void *stream);
+
+/* Catalogue coverage per cutoff: how many distinct items the first c entries of all rows touch (upstream has no such
+ * number; a caller of MARK_MAPK, src/lightgcn.py:184-190, would count the union of its top_rlvnt_itm lists on the host).
+ *   topk, topk_stride, k, n_rows   as lgc_rank_metrics; cutoffs, n_cut as there (the same error codes)
+ *   n_items    entries are item indices in [0, n_items); n_items >= 1 (LGC_E_INVAL otherwise), below 2^31 (LGC_E_RANGE)
+ *   bitmap     uint32 [n_cut, ceil(n_items / 32)], zeroed by the caller before the FIRST call: row ci gets, by integer
+ *              atomic OR, a bit for every item among the first cutoffs[ci] entries of every row
+ *   counts     int64 [n_cut]: overwritten with the number of set bits of the whole bitmap row -- a second call with
+ *              further rows (the next request) and the same bitmap accumulates
+ *   status     an entry outside [0, n_items) sets LGC_ST_INDEX_OOB and marks nothing (it is range-checked before any
+ *              address is formed from it) */
+int lgc_topk_coverage(const int64_t *topk, int64_t topk_stride, int32_t k, int64_t n_rows, const int32_t *cutoffs,
+                      int32_t n_cut, int64_t n_items, uint32_t *bitmap, int64_t *counts, int32_t *status, void *stream);
+
 /* ---------------------------------------------------------------------------------------
  * Hop distances and shortest paths from users to their recommended items (InferenceLightGCN.compute_paths,
  * src/inference_lightgcn.py:85-119: per pair has_path + shortest_path_length + shortest_path of networkx on the host).
