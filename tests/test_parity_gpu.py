@@ -1435,7 +1435,7 @@ def test_adam_over_row_ranges_and_foreign_state(device, dim):
 
 @pytest.mark.parametrize("m", [1, 5, 777, 4096, 8192, 9000])
 def test_seed_prepare_is_a_stable_sort_with_the_destination_lists(device, m):
-    """lgc_seed_prepare (one workgroup, bitonic sort in LDS) against the same steps in torch: sorted ids with "no row"
+    """lgc_seed_prepare (m / 8 workgroups rank the ids by counting, one more launch derives the lists) against the same steps in torch: sorted ids with "no row"
     for ids outside the table, the stable permutation, the three destination lists and the pull's column map; above
     LGC_SEED_MAX ids the torch steps run instead (m = 9000)."""
     from gnn_ecommerce_amd import propagate
