@@ -8,6 +8,7 @@ The directory is called ``gnn-ecommerce_amd`` (not an importable name); ``import
 resolves to it through the shim package of that name at the repository root.
 """
 from . import _native
+from .foldin import SessionLists, fold_in, fold_table
 from .graph import PropGraph, build_row_plan, clear_cache, get_graph
 from .lgconv import LGConv
 from .lightgcn import BPRLoss, LightGCN, regularization_loss
@@ -21,4 +22,5 @@ from .trainer import PartitionedTrainer
 __all__ = ["LightGCN", "BPRLoss", "LGConv", "PropGraph", "get_graph", "clear_cache", "build_row_plan",
            "propagate_sum", "hop", "pair_dot", "check_index_status", "TripleSampler", "regularization_loss", "PartitionedTrainer", "_native",
            "SeenLists", "PositiveLists", "score_rows", "recommend_topk", "hop_distances", "shortest_paths", "paths_frame", "compute_paths",
-           "rank_metrics", "evaluate_ranking", "overlap_items", "metrics_frame", "RankingResult"]
+           "rank_metrics", "evaluate_ranking", "overlap_items", "metrics_frame", "RankingResult",
+           "SessionLists", "fold_table", "fold_in"]

@@ -9,7 +9,9 @@ src/inference_lightgcn.py and torchserve/lightgcn_handler.py run unchanged
 ``recommendation_loss``.  ``recommend_topk`` and ``evaluateK`` are additions: the epoch's evaluation
 (``recommendK`` over all validation users, then ``MARK_MAPK``) in bounded device memory; ``evaluate_metrics`` adds NDCG, MAP, MRR,
 hit rate and coverage at several cutoffs from the same single ranking pass; ``recommendation_paths`` is one too: hop
-distances and shortest paths from users to their recommended items (src/inference_lightgcn.py:85-119).  What changes is underneath: propagation is the HIP CSR-SpMM with
+distances and shortest paths from users to their recommended items (src/inference_lightgcn.py:85-119); ``embed_sessions`` and
+``recommend_sessions`` answer for nodes outside the table -- new visitors, known users with a fresh list -- from their
+interaction lists (``foldin``).  What changes is underneath: propagation is the HIP CSR-SpMM with
 the layer sum fused (``propagate.propagate_sum``) and pair scoring is one gather-dot kernel.
 """
 from __future__ import annotations
@@ -22,6 +24,7 @@ from torch import Tensor
 from torch.nn.modules.loss import _Loss
 
 from . import _native
+from .foldin import SessionLists, fold_in, fold_table
 from .graph import get_graph
 from .lgconv import LGConv
 from .paths import shortest_paths
@@ -63,6 +66,8 @@ class LightGCN(torch.nn.Module):
         # weights nor alpha changed; set to False to recompute on every request like the reference
         self.cache_recommend_embeddings = True
         self._served = None
+        self._fold = None                 # foldin.fold_table's table, kept under the same key as _served
+        self.fold_tables_built = 0        # how often it was computed (cache hits do not count)
         self.reset_parameters()
 
     def reset_parameters(self):
@@ -106,12 +111,13 @@ class LightGCN(torch.nn.Module):
 
     def invalidate(self) -> None:
         """Forget every derived table: the cached graphs of this process and the propagated table ``recommendK``
-        reuses.  The caches key on tensor identity + version counter, which in-place torch ops bump; call this after
+        reuses and the fold-in table beside it.  The caches key on tensor identity + version counter, which in-place torch ops bump; call this after
         writes that do not (``weight.data.copy_``, a DLPack/numpy alias, a foreign kernel).  The reference re-derives
         everything on every call."""
         from .graph import clear_cache
         clear_cache()
         self._served = None
+        self._fold = None
         self._alpha_host = None
 
     def forward(self, edge_index, edge_label_index: Optional[Tensor] = None,
@@ -253,6 +259,47 @@ class LightGCN(torch.nn.Module):
         targets = (top_items.to(device=graph.device, dtype=torch.int64) + int(n_users)).contiguous()
         dist, paths = shortest_paths(graph, ids, targets, max_len=max_len, workspace_bytes=workspace_bytes, trace=trace)
         return dist, (dist > 3).any(dim=1), paths
+
+    # -- nodes outside the table: fold-in -------------------------------------------------------
+    def embed_sessions(self, edge_index, edge_weight, n_users, n_items, sessions: SessionLists, init_users=None) -> Tensor:
+        """fp32 ``[n_rows, D]``: for every interaction list of ``sessions`` the embedding ``get_embedding`` would give a
+        node appended to the graph with one-way edges from the listed items (``foldin``) -- a visitor the model was not
+        trained on.  ``init_users`` (int64 tensor or list, one id per session): the trained user whose layer-0 row the
+        node starts from -- a known user with a fresh list; with its own edge list the result is its served row --,
+        -1 for an unknown visitor (a zero row); None = all unknown."""
+        w = self.embedding.weight
+        _native.require_device(w, "LightGCN.embedding.weight")
+        normalize = self.convs[0].normalize if self.num_layers > 0 else True
+        graph = get_graph(edge_index, edge_weight, self.num_nodes, normalize)
+        n_users, n_items = int(n_users), int(n_items)
+        if graph.split != n_users or n_users + n_items != self.num_nodes:
+            raise ValueError(f"fold-in needs the user|item graph split at n_users: split {graph.split}, n_users {n_users}, "
+                             f"n_items {n_items}, {self.num_nodes} nodes")
+        fold = fold_table(self, graph)
+        sessions.validate(n_items)
+        init_table = init_rows = None
+        if init_users is not None:
+            if not torch.is_tensor(init_users):
+                ids = [int(u) for u in init_users]
+                if any(u < -1 or u >= n_users for u in ids):
+                    raise ValueError(f"init_users must be -1 or lie in [0, {n_users})")
+                init_users = torch.tensor(ids, dtype=torch.int64)
+            init_rows = init_users.reshape(-1).to(device=w.device, dtype=torch.int64).contiguous()
+            init_table = w.detach()[:n_users]
+        return fold_in(fold, graph.dis[n_users:] if graph.normalize else None, sessions, init_table, init_rows,
+                       self._alphas()[0], graph.normalize)
+
+    def recommend_sessions(self, edge_index, edge_weight, n_users, n_items, sessions: SessionLists, init_users=None,
+                           k: int = 20, mask="purchased", return_values: bool = False,
+                           workspace_bytes: int = DEFAULT_WORKSPACE_BYTES):
+        """int64 ``[n_rows, k]`` item indices on the device: ``recommend_topk`` with the folded rows of
+        ``embed_sessions`` as the user table.  ``mask``: which of a session's own items are zeroed like seen items --
+        ``"purchased"`` (weight 1.0, upstream's rule for the seen matrix), ``"all"`` or None.  The score matrix exists
+        one panel of ``workspace_bytes`` at a time; with ``return_values`` also the masked scores."""
+        rows = self.embed_sessions(edge_index, edge_weight, n_users, n_items, sessions, init_users)
+        item_t = self._serving_embedding(edge_index, edge_weight).detach()[int(n_users):]
+        sel = torch.arange(rows.size(0), dtype=torch.int64, device=rows.device)
+        return recommend_topk(rows, sel, item_t, sessions.mask(mask), k, workspace_bytes, return_values)
 
     def link_pred_loss(self, pred: Tensor, edge_label: Tensor, **kwargs) -> Tensor:
         return torch.nn.BCEWithLogitsLoss(**kwargs)(pred, edge_label.to(pred.dtype))

@@ -8,7 +8,11 @@ returns what upstream returns, ``[{'items': [[k item indices], ...]}]``.  What d
     rebuilding the COO (lightgcn_handler.py:32-38), and keeps the purchased-items lists on the device as a CSR;
   * ``inference`` calls ``LightGCN.recommendK`` with the graph object and the purchase lists (``SeenLists``): the K-layer
     propagate is reused across requests, scores / mask / top-k stay on the device (lgc_mask_topk builds the request's
-    mask rows as bitmasks in LDS; the dense ``[n_sel, n_items]`` mask upstream materialises never exists).
+    mask rows as bitmasks in LDS; the dense ``[n_sel, n_items]`` mask upstream materialises never exists);
+  * ``inference`` also answers for visitors the model was not trained on: next to a plain user id a request element may be
+    ``{"items": [...], "weights": [...] (optional), "user": id (optional)}`` -- the items the visitor looked at, put in
+    the cart or bought (relabelled item indices, as the answers), upstream's event weights, and for a known user with a
+    fresh list the user whose trained layer-0 row to start from (``LightGCN.recommend_sessions``, fold-in).
 """
 from __future__ import annotations
 
@@ -18,6 +22,7 @@ from typing import List
 import torch
 
 from . import _native
+from .foldin import SessionLists
 from .graph import PropGraph
 from .lightgcn import LightGCN
 from .propagate import SeenLists
@@ -86,7 +91,43 @@ class RecommendHandler:
         out[rows, self.seen_items[pos]] = 1.0
         return out
 
+    def parse_sessions(self, data):
+        """A request with at least one dict element, split by kind: ``(id_pos, ids, session_pos, lists, init_users)`` --
+        the positions and values of the plain user ids, the positions of the dict elements, their ``(items, weights)``
+        pairs and the user each starts from (-1: none).  A malformed element raises ValueError."""
+        id_pos, ids, session_pos, lists, init_users = [], [], [], [], []
+        for pos, el in enumerate(data):
+            if isinstance(el, dict):
+                unknown = set(el) - {"items", "weights", "user"}
+                if unknown or "items" not in el:
+                    raise ValueError(f"request element {pos}: expected 'items' and optionally 'weights', 'user'; got {sorted(el)}")
+                items, weights, user = el["items"], el.get("weights"), el.get("user")
+                if not isinstance(items, (list, tuple)) or any(isinstance(i, bool) or not isinstance(i, int) for i in items):
+                    raise ValueError(f"request element {pos}: 'items' must be a list of item indices")
+                if any(i < 0 or i >= self.n_items for i in items):
+                    raise ValueError(f"request element {pos}: item index outside [0, {self.n_items})")
+                if weights is not None:
+                    if (not isinstance(weights, (list, tuple))
+                            or any(isinstance(w, bool) or not isinstance(w, (int, float)) for w in weights)):
+                        raise ValueError(f"request element {pos}: 'weights' must be a list of numbers")
+                    if len(weights) != len(items):
+                        raise ValueError(f"request element {pos}: {len(items)} items but {len(weights)} weights")
+                if user is not None:
+                    if isinstance(user, bool) or not isinstance(user, int) or user < 0 or user >= self.n_users:
+                        raise ValueError(f"request element {pos}: 'user' outside [0, {self.n_users})")
+                session_pos.append(pos)
+                lists.append((list(items), None if weights is None else list(weights)))
+                init_users.append(-1 if user is None else user)
+            elif isinstance(el, int) and not isinstance(el, bool):
+                id_pos.append(pos)
+                ids.append(el)
+            else:
+                raise ValueError(f"request element {pos}: expected a user id or a dict with 'items', got {type(el).__name__}")
+        return id_pos, ids, session_pos, lists, init_users
+
     def inference(self, data, *args, **kwargs):
+        if any(isinstance(el, dict) for el in data):
+            return self._inference_sessions(data)
         users = [int(u) for u in data]
         if any(u < 0 or u >= self.n_users for u in users):      # upstream's embedding gather raises IndexError as well
             raise IndexError(f"user index outside [0, {self.n_users})")
@@ -94,6 +135,25 @@ class RecommendHandler:
             # the purchase lists stay a CSR on the device; lgc_mask_topk turns the request's rows into LDS bitmasks
             frame = self.model.recommendK(self.graph, None, self.n_users, self.n_items, self.seen, list(data), self.k)
             return {"items": list(frame["top_rlvnt_itm"])}
+
+    def _inference_sessions(self, data):
+        """A request that holds interaction lists: the dict elements go through ``recommend_sessions`` in one batch, the
+        plain ids through ``recommendK`` as a request of ids alone would; the answers come back in request order."""
+        id_pos, ids, session_pos, lists, init_users = self.parse_sessions(data)
+        if any(u < 0 or u >= self.n_users for u in ids):
+            raise IndexError(f"user index outside [0, {self.n_users})")
+        answers = [None] * len(data)
+        with torch.no_grad():
+            sessions = SessionLists.from_lists(lists, self.device).validate(self.n_items, "request")
+            top = self.model.recommend_sessions(self.graph, None, self.n_users, self.n_items, sessions,
+                                                init_users if any(u >= 0 for u in init_users) else None, self.k)
+            if ids:
+                frame = self.model.recommendK(self.graph, None, self.n_users, self.n_items, self.seen, ids, self.k)
+                for pos, row in zip(id_pos, frame["top_rlvnt_itm"]):
+                    answers[pos] = row
+            for pos, row in zip(session_pos, top.cpu().tolist()):
+                answers[pos] = row
+        return {"items": answers}
 
     def postprocess(self, data) -> List[dict]:
         return [data]

@@ -527,6 +527,44 @@ int lgc_mask_topk(const float *scores, int64_t score_stride, const float *seen, 
                   int32_t n_cols, int32_t k, int64_t *out_index, float *out_value, void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Fold-in: the embedding of a node that is NOT a row of the trained table -- a visitor the model has never seen, or a
+ * known user whose list changed after training -- from the items it interacted with.  Upstream has no such path: its
+ * handler gathers a trained row per requested id (torchserve/lightgcn_handler.py:73-96) out of the table that
+ * `get_embedding` propagates (src/lightgcn.py:91-99), and an id outside the table raises.  What this computes is exactly
+ * the row src/lightgcn.py:91-99 gives a node appended to the trained graph with ONE-WAY edges i_k -> node (weights w_k) and
+ * layer-0 row z; one-way edges leave every existing degree and row untouched:
+ *     out[r] = a0 * init[init_rows[r]] + sum_k c_k * fold[i_k],   c_k = item_dis[i_k] * w_k * d,   d = (sum_k w_k)^-1/2
+ * with fold = sum_{l=0..K-1} alpha_{l+1} * x_l[items], one [n_items, dim] table per model and graph (the caller computes it
+ * once: the layer sum with the coefficients shifted by one).
+ *   list_ptr    int64 [n_rows + 1], list_items int64: the lists as a CSR of item indices in [0, n_items) WITHOUT the
+ *               n_users offset -- lgc_mask_topk's list form with list_rows = NULL, so the same two arrays mask the scores.
+ *               list_ptr is read on trust (as lgc_mask_topk reads its lists)
+ *   list_weight fp32 per entry, or NULL = all ones
+ *   item_dis    fp32 [n_items]: the item slice of the graph's dis (lgc_build_csr's dis_out); required with normalize = 1,
+ *               ignored with normalize = 0 (then c_k = w_k)
+ *   fold        fp32 [n_items, dim], rows fold_stride floats apart; n_items >= 1
+ *   init_rows   int64 [n_rows] or NULL: an id in [0, n_init_rows) adds a0 * init[id] (init fp32, rows init_stride apart);
+ *               -1 = no row; any other id sets LGC_ST_INDEX_OOB and adds nothing
+ *   out         fp32 [n_rows, dim], rows out_stride apart; EVERY row is written: an empty list, or one whose weights sum
+ *               to 0 (d = 0, as lgc_build_csr's dis), gives a0 * init or zeros
+ * Arithmetic (the build's and the hop's own, so the identity holds to rounding): the degree is the fp32 sum of the list's
+ * weights taken sequentially in list order; d = 1 / sqrt(deg), both correctly rounded, inf -> 0; c_k = (item_dis * w) * d left
+ * to right, each product rounded; every product is rounded before its add; the a0 * init term is added last.  An item
+ * outside [0, n_items) is skipped altogether -- it is left out of the degree too -- and sets LGC_ST_INDEX_OOB; the index is
+ * range-checked before any address is formed from it.  Negative weights behave as in lgc_build_csr.  Lists of up to 32
+ * entries are summed in list order (the short-row contract of lgc_spmm / lgc_spmm_tiles); longer ones in a fixed order
+ * that depends only on dim and the pointers' alignment.  No float atomics: the same bits on every run.
+ * One wavefront per row; 16-byte loads where dim % 4 == 0 and all rows are 16-byte aligned, dword loads otherwise.
+ * Errors before any launch: LGC_E_DIM (as lgc_dim_ok); LGC_E_INVAL (a null required pointer, a negative size, n_items < 1,
+ * a stride below dim, normalize outside {0, 1}, normalize = 1 without item_dis, init_rows without init); LGC_E_RANGE
+ * (n_rows or n_items >= 2^31).  n_rows == 0 validates, launches nothing and returns 0.
+ * ------------------------------------------------------------------------------------- */
+int lgc_fold_in(const int64_t *list_ptr, const int64_t *list_items, const float *list_weight, int64_t n_rows,
+                const float *item_dis, const float *fold, int64_t fold_stride, int64_t n_items,
+                const int64_t *init_rows, const float *init, int64_t init_stride, int64_t n_init_rows, float a0,
+                int32_t normalize, int32_t dim, float *out, int64_t out_stride, int32_t *status, void *stream);
+
+/* ---------------------------------------------------------------------------------------
  * Epoch evaluation (TrainLightGCN.test, src/train_lightgcn.py:155-162: recommendK over all validation users,
  * then MARK_MAPK): scores, ranking and metrics in bounded device memory.  A caller walks its users in panels:
  * lgc_score_rows -> lgc_mask_topk (list form, list_rows = the panel's users) per panel, then lgc_topk_hits and

@@ -63,5 +63,15 @@ with tempfile.TemporaryDirectory() as d:
         h.handle([{"body": list(range(r, r + 64))}])
         ts.append((time.perf_counter() - t0) * 1e3)
     out["request_64_users_ms"] = round(statistics.median(ts[3:]), 3)
+    # a visitor the model was not trained on (fold-in), next to a known user in one request
+    visitor = {"items": [3, 17, 42], "weights": [1.0, 0.1, 0.01]}
+    mixed = h.handle([{"body": [7, visitor, {"items": [5], "user": 7}]}])
+    ts = []
+    for r in range(30):
+        t0 = time.perf_counter()
+        h.handle([{"body": [dict(visitor, items=[3 + r, 17, 42])]}])
+        ts.append((time.perf_counter() - t0) * 1e3)
+    out["request_1_visitor_ms"] = round(statistics.median(ts[5:]), 3)
+    out["mixed_response_rows"] = [len(row) for row in mixed[0]["items"]]
     out["response_shape"] = [len(first), list(first[0]), len(first[0]["items"]), len(first[0]["items"][0])]
 print(json.dumps(out))
