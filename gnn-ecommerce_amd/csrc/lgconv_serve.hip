@@ -9,7 +9,8 @@ namespace {
 // Serving tail: multiplicative seen-mask + top-k per row, on the device
 // ----------------------------------------------------------------------------------------
 // masked[i] = score[i] * (1 - seen[i])  (src/lightgcn.py:175 -- seen items become 0, they are not removed), then the
-// k largest by (value descending, index ascending).  One workgroup per row.  Rows of up to 65,536 columns are read
+// k largest by (value descending, index ascending); every NaN, of either sign bit, ranks above +inf as in torch.topk,
+// and -0 equals +0 (order_key).  One workgroup per row.  Rows of up to 65,536 columns are read
 // ONCE: each thread keeps its 64 order-preserving keys in registers.  Short cut: the k-th largest of the 1,024
 // per-thread maxima bounds the k-th largest element from below; the few elements in or above its 11-bit bin go to a
 // list in LDS and each counts the entries ahead of it (= its output position).  Heavily tied or flat rows (list
@@ -19,9 +20,14 @@ namespace {
 constexpr int kTopkMax = 256;
 constexpr int kTopkBlock = 1024;   // 16 wavefronts on one row: a single-row request is latency-bound on one CU
 
+// Ascending with the value.  Every NaN, whatever its sign bit and payload, takes the one top key: torch.topk ranks NaN
+// as the largest value, and the sign of the NaN a seen +-inf score turns into (inf * 0) is the hardware's choice.  Equal
+// keys are ordered by index, so NaNs come first by index, then +inf, the finite values (-0 = +0), then -inf.
 __device__ __forceinline__ uint32_t order_key(float v) {
-    const uint32_t u = __float_as_uint(__fadd_rn(v, 0.0f));   // -0 -> +0: they compare equal (a seen item's 0 * score)
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);        // ascending with the value; +NaN above +inf like torch.topk
+    const float w = __fadd_rn(v, 0.0f);                       // -0 -> +0: they compare equal (a seen item's 0 * score)
+    const uint32_t u = __float_as_uint(w);
+    const uint32_t key = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+    return w != w ? 0xFFFFFFFFu : key;
 }
 
 constexpr int kTopkRegs = 64;      // keys a thread can hold: rows up to kTopkRegs * kTopkBlock columns are read once
@@ -70,8 +76,8 @@ __global__ __launch_bounds__(kTopkBlock) void k_mask_topk(const float *__restric
         if (MASK == 2) return (seen_bits[i >> 5] >> (i & 31)) & 1u ? __fmul_rn(s, 0.0f) : s;
         return MASK == 1 ? __fmul_rn(s, __fsub_rn(1.0f, m)) : s;
     };
-    // slots past the row end hold key 0, below every real key (real keys are lifted to >= 1: only the one -NaN
-    // pattern 0xFFFFFFFF moves, onto its neighbour), so the passes need no bounds test.  Loads are clamped, not
+    // slots past the row end hold key 0, below every real key (real keys are lifted to >= 1; the smallest one a value
+    // has is -inf's 0x007FFFFF, so the lift moves nothing), so the passes need no bounds test.  Loads are clamped, not
     // predicated: no divergent control flow around them.
     auto key_of = [&](float s, float m, int i) {
         const uint32_t key = max(order_key(masked_at(s, m, min(i, n_cols - 1))), 1u);

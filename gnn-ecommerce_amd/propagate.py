@@ -1050,7 +1050,9 @@ class PositiveLists:
 
 def mask_topk(scores: Tensor, seen, k: int) -> Tensor:
     """Indices [rows, k] (int64, on the device) of the k largest ``scores * (1 - seen)`` per row, ties by lower index
-    (src/lightgcn.py:175-177).  ``seen``: a dense fp32 tensor, a ``SeenLists``, or None.  k <= 256."""
+    (src/lightgcn.py:175-177).  The order: every NaN first (either sign bit, as torch.topk ranks them), then +inf, the
+    finite values with -0 equal to +0, then -inf; equal elements, NaNs among them, by ascending index.
+    ``seen``: a dense fp32 tensor, a ``SeenLists``, or None.  k <= 256."""
     lists = seen if isinstance(seen, SeenLists) else None
     if lists is not None:
         seen = None

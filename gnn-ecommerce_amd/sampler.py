@@ -11,7 +11,9 @@ the ignore set, :169-173,179) for each of them.  Same return value: three int64 
 ``(users, pos_items, neg_items)``, item ids already offset by ``n_users`` -- on the device, so the
 ``.to(device)`` copies of train_lightgcn.py:133-135 become no-ops.
 
-Random streams cannot match Python's ``random``; what is tested is the distribution and the constraints.
+Random streams cannot match Python's ``random``; what is tested is the distribution and the constraints, and -- the
+kernel being a pure function draw(seed, step, sample, attempt) -- every triple against a restatement of the stream in
+Python integers (tests/sampler_support.py), so a seed reproduces a training run.
 """
 from __future__ import annotations
 

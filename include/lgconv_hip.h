@@ -515,7 +515,8 @@ int lgc_pair_dot(const float *emb, int64_t stride, int32_t dim, int64_t n_nodes,
 /* Serving tail of LightGCN.recommendK (src/lightgcn.py:175-177; called per request from
  * torchserve/lightgcn_handler.py:91): masked = scores * (1 - seen), then per row the k largest by
  * (value descending, index ascending), entirely on the device -- upstream copies the [rows, n_cols] score matrix
- * to the host first.  k <= 256 (LGC_E_RANGE beyond).  The mask comes in one of two forms (or neither: NULL, NULL):
+ * to the host first.  The full order: every NaN (either sign bit) first, then +inf, the finite values with -0 = +0,
+ * then -inf; equal elements by ascending index.  k <= 256 (LGC_E_RANGE beyond).  The mask comes in one of two forms (or neither: NULL, NULL):
  *   dense   seen fp32 [n_rows, n_cols], any values -- what upstream's handler builds per request
  *           (index_select on the sparse purchase matrix + to_dense, lightgcn_handler.py:88);
  *   lists   list_ptr int64 [n_users + 1], list_items int64 (a CSR of the purchase matrix, seen = 1 for listed
