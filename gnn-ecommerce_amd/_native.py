@@ -164,6 +164,15 @@ SIGNATURES = {
                                    c_uint64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "lgc_pair_dot": (c_int, [c_void_p, c_int64, c_int32, c_int64, c_void_p, c_void_p, c_int64, c_void_p,
                              c_void_p, c_void_p]),
+    "lgc_reduce_workspace_bytes": (c_size_t, [c_int64, c_int64]),
+    "lgc_reduce_count": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int32, c_void_p, c_size_t, c_void_p, c_void_p,
+                                 c_void_p]),
+    "lgc_reduce_fill": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_void_p,
+                                c_void_p, c_void_p]),
+    "lgc_reduce_gram_workspace_bytes": (c_size_t, [c_int64]),
+    "lgc_reduce_gram_count": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_size_t,
+                                      c_void_p, c_void_p]),
+    "lgc_reduce_gram_fill": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
 }
 
 

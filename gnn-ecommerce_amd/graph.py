@@ -723,6 +723,110 @@ def apply_rows(op: "Operator", rows: Tensor, x: Tensor, out: Tensor, a: float = 
     return out
 
 
+# Middle-hop reduction (lgc_reduce_*, PropGraph.reduced): users whose row has at most T entries -- and whom at most T item
+# rows name -- leave the middle layers of bipartite_sum; their two-step paths run as the item x item operator G_L instead.
+# "0": off; an integer: that T; "auto": T = ELIMINATE_AUTO_MAX_DEG, and only where the full item half takes the band sweep (a
+# user table far beyond the caches) and nnz(G_L) is at most ELIMINATE_MAX_GRAM_SHARE times the entries taken out of the CSR
+# (both halves counted) -- a graph with heavier hubs, whose G_L outgrows what it replaces, keeps the plain path.
+# Measured on the cosmetics graph (profiles/EXPERIMENTS.md, "Middle-hop reduction"): T = 3 is the fastest at D=64 / K=3
+# (-2.0 %) and at D=90 / K=5 (-4.1 %); its G_L holds 0.82 entries per entry removed.  T = 4 (1.12) still gains at D=64 but
+# not at D=90, T >= 5 (1.37 and up) loses: the share limit 1.0 separates the T that pay from those that do not.
+ELIMINATE_MAX_DEG = os.environ.get("LGCN_ELIMINATE_MAX_DEG", "auto")
+ELIMINATE_AUTO_MAX_DEG = int(os.environ.get("LGCN_ELIMINATE_AUTO_MAX_DEG", "3"))
+ELIMINATE_MAX_GRAM_SHARE = float(os.environ.get("LGCN_ELIMINATE_MAX_GRAM_SHARE", "1.0"))
+# G_L's rows are long (mean 89 entries at T = 4 on the cosmetics graph, the longest 23.6 k) and gather from the small item
+# table: their own chunk length
+GRAM_CHUNK_LEN = int(os.environ.get("LGCN_GRAM_CHUNK_LEN", "256"))
+
+
+@dataclass
+class ReducedCSR:
+    """What the native builder returns (``build_reduced_csr``): the reduced graph and G_L in compact numbering."""
+    max_deg: int
+    n_h: int                    # kept users: rows 0 .. n_h - 1; item i is row and column n_h + i
+    n_items: int
+    user_map: Tensor            # int32 [split]: new id of a kept user, -1 of an eliminated one
+    rowptr: Tensor              # int32 [n_h + n_items + 1]
+    entries: Tensor             # int32 [nnz, 2]
+    user_nnz: int               # entries of the kept user rows
+    n_pairs: int                # expanded (item, item) pairs before merging
+    gram_rowptr: Tensor         # int32 [n_h + n_items + 1], user rows empty
+    gram_entries: Tensor        # int32 [nnz(G_L), 2]
+
+    @property
+    def nnz(self) -> int:
+        return self.entries.size(0)
+
+    @property
+    def gram_nnz(self) -> int:
+        return self.gram_entries.size(0)
+
+
+def build_reduced_csr(rowptr: Tensor, entries: Tensor, split: int, num_nodes: int, max_deg: int) -> Optional[ReducedCSR]:
+    """lgc_reduce_count / _fill / _gram_count / _gram_fill on a forward CSR: two host syncs (the sizes).  None when the
+    expanded pair count does not fit int32 (LGC_E_RANGE): the caller then runs without elimination."""
+    lib = _native.load()
+    _native.require_device(rowptr, "rowptr")
+    dev = rowptr.device
+    n_edges = entries.size(0)
+    n_items = num_nodes - split
+    u8 = dict(dtype=torch.uint8, device=dev)
+    i32 = dict(dtype=torch.int32, device=dev)
+    ws_bytes = lib.lgc_reduce_workspace_bytes(num_nodes, n_edges)
+    ws = torch.empty(max(ws_bytes, 1), **u8)
+    user_map = torch.empty(max(split, 1), **i32)
+    totals = torch.empty(4, dtype=torch.int64, device=dev)
+    args = (_native.ptr(rowptr), _native.ptr(entries), num_nodes, n_edges, split)
+    with torch.cuda.device(dev):
+        st = _native.stream_of(dev)
+        _native.check(lib.lgc_reduce_count(*args, int(max_deg), _native.ptr(ws), ws_bytes, _native.ptr(user_map),
+                                           _native.ptr(totals), st), "lgc_reduce_count")
+        n_h, user_nnz, nnz, n_pairs = totals.tolist()                       # sync 1
+        rowptr_h = torch.empty(n_h + n_items + 1, **i32)
+        entries_h = torch.empty((nnz, 2), **i32)
+        _native.check(lib.lgc_reduce_fill(*args, _native.ptr(ws), _native.ptr(user_map), n_h, nnz, _native.ptr(rowptr_h),
+                                          _native.ptr(entries_h) if nnz else None, st), "lgc_reduce_fill")
+        gws_bytes = lib.lgc_reduce_gram_workspace_bytes(n_pairs)
+        if gws_bytes == 0:
+            return None
+        gws = torch.empty(gws_bytes, **u8)
+        total = torch.empty(1, dtype=torch.int64, device=dev)
+        code = lib.lgc_reduce_gram_count(*args, _native.ptr(ws), n_pairs, _native.ptr(gws), gws_bytes, _native.ptr(total), st)
+        if code == -4:
+            return None
+        _native.check(code, "lgc_reduce_gram_count")
+        gram_nnz = int(total.item())                                        # sync 2
+        gram_rowptr = torch.empty(n_h + n_items + 1, **i32)
+        gram_entries = torch.empty((gram_nnz, 2), **i32)
+        _native.check(lib.lgc_reduce_gram_fill(_native.ptr(gws), n_pairs, n_h, n_items, gram_nnz, _native.ptr(gram_rowptr),
+                                               _native.ptr(gram_entries) if gram_nnz else None, st), "lgc_reduce_gram_fill")
+    return ReducedCSR(int(max_deg), n_h, n_items, user_map[:split], rowptr_h, entries_h, user_nnz, n_pairs, gram_rowptr,
+                      gram_entries)
+
+
+@dataclass
+class ReducedGraph:
+    """The operators of the middle layers with the low-degree users eliminated (``PropGraph.reduced``).  All three work
+    on table views that start at row ``offset`` of a full table: kept user h is row h of the view, item i row n_h + i --
+    row split + i of the full table, where the full operators address it."""
+    csr: ReducedCSR
+    n_h: int
+    offset: int
+    user_op_h: Optional[Operator]       # None when no user is kept
+    item_op_h: Optional[Operator]       # None when the kept users leave the item rows empty
+    gram_op: Optional[Operator]         # None when G_L is empty
+
+    def nbytes(self) -> int:
+        c = self.csr
+        total = sum(t.numel() * 4 for t in (c.user_map, c.rowptr, c.entries, c.gram_rowptr, c.gram_entries))
+        for op in (self.user_op_h, self.item_op_h, self.gram_op):
+            if op is not None:
+                total += op.plan.chunks.numel() * 4 + sum(tc.slab.numel() * 4 + tc.order.numel() * 4 + tc.meta.numel() * 4
+                                                          for tc in (op._tiles or []))
+                total += sum(sw.nbytes() for sw in op._sweep.values())
+        return total
+
+
 def sweep_choice(lib, dim: int, table_rows: int, stride: int) -> int:
     """Which band-sweep plan a gathered table of this width gets: 4 / 2 (entries per step), 0 = chunk path."""
     sweep = int(lib.lgc_sweep_ok(dim, table_rows, stride))
@@ -829,6 +933,51 @@ class PropGraph:
             self._halves[transpose] = got
         return got
 
+    eliminate_max_deg: Optional[int] = None     # forces T for this graph (0 = off); None: the LGCN_ELIMINATE_MAX_DEG knob
+
+    def reduced(self, transpose: bool = False) -> Optional[ReducedGraph]:
+        """The middle-layer operators with the low-degree users eliminated (module comment at ELIMINATE_MAX_DEG), or None
+        when elimination is off for this graph: not bipartite, the transposed operator (it keeps the plain path),
+        T = 0, "auto" on a graph whose item half does not take the band sweep or whose G_L is too large, or a pair count
+        beyond int32.  Built once per T and cached like ``halves``."""
+        if transpose or self.split is None:
+            return None
+        forced = self.eliminate_max_deg
+        auto = forced is None and ELIMINATE_MAX_DEG == "auto"
+        max_deg = int(forced) if forced is not None else (ELIMINATE_AUTO_MAX_DEG if auto else int(ELIMINATE_MAX_DEG))
+        if max_deg <= 0:
+            return None
+        key = ("reduced", max_deg, auto)
+        if key in self._halves:
+            return self._halves[key]
+        got = None
+        if not auto or self.halves(False)[1].sweep_cols is not None:
+            got = self._build_reduced(max_deg)
+            if got is not None and auto:
+                removed = self.forward_op.nnz - got.csr.nnz
+                if got.csr.gram_nnz > ELIMINATE_MAX_GRAM_SHARE * removed:
+                    got = None
+        self._halves[key] = got
+        return got
+
+    def _build_reduced(self, max_deg: int) -> Optional[ReducedGraph]:
+        op = self.forward_op
+        csr = build_reduced_csr(op.rowptr, op.entries, self.split, self.num_nodes, max_deg)
+        if csr is None:
+            return None
+        n_h, n_rows = csr.n_h, csr.n_h + csr.n_items
+        user_chunk = max(self.chunk_len, USER_CHUNK_LEN)
+        user_op_h = item_op_h = gram_op = None
+        if n_h > 0:
+            user_op_h = Operator.build(n_rows, csr.rowptr, csr.entries, 0, n_h, self.short_max, user_chunk,
+                                       sweep_cols=(n_h, n_rows))
+        if csr.nnz - csr.user_nnz > 0:
+            item_op_h = Operator.build(n_rows, csr.rowptr, csr.entries, n_h, n_rows, self.short_max, self.chunk_len,
+                                       sweep_cols=(0, n_h))
+        if csr.gram_nnz > 0:
+            gram_op = Operator.build(n_rows, csr.gram_rowptr, csr.gram_entries, n_h, n_rows, self.short_max, GRAM_CHUNK_LEN)
+        return ReducedGraph(csr, n_h, self.split - n_h, user_op_h, item_op_h, gram_op)
+
     def prepare(self, dim: int, table_rows: Optional[int] = None, transpose: bool = False) -> "PropGraph":
         """Build, now, every work plan a propagation of width ``dim`` will use (they are otherwise built lazily inside
         the first hop): tile classes of the short rows (device index arithmetic + lgc_build_tiles), and for a
@@ -838,8 +987,12 @@ class PropGraph:
         rows = self.num_nodes if table_rows is None else int(table_rows)
         stride = dim if dim % 32 == 0 else (dim + 31) // 32 * 32            # propagate.scratch_table's row stride
         ops = self.halves(transpose) if self.split is not None else ((self.transpose_op if transpose else self.forward_op),)
+        ops = [(op, rows) for op in ops]
+        red = self.reduced(transpose)
+        if red is not None:                                   # the middle layers' operators work on views of rows - offset rows
+            ops += [(op, max(rows - red.offset, 0)) for op in (red.user_op_h, red.item_op_h, red.gram_op) if op is not None]
         import time
-        for op in ops:
+        for op, rows in ops:
             t0 = time.perf_counter()
             if op.tiled and dim >= 4:
                 op.tiles

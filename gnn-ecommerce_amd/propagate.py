@@ -93,7 +93,7 @@ class _HopSpan:
 
 
 def bipartite_sum(user_op: Operator, item_op: Operator, split: int, x0: Tensor, alphas: Sequence[float],
-                  final_rows: Optional[Tensor] = None) -> Tensor:
+                  final_rows: Optional[Tensor] = None, reduced=None) -> Tensor:
     """sum_l alpha_l A^l x0 for A = [[0, R], [R^T, 0]] (users first), K = len(alphas) - 1 layers.
 
     With x_l = A^l x0:  x_l[items] = R^T x_{l-1}[users]  (item step, gathers user rows) and
@@ -110,6 +110,17 @@ def bipartite_sum(user_op: Operator, item_op: Operator, split: int, x0: Tensor, 
     same bits for rows of up to 32 entries), and the LAST item step -- otherwise a full sweep over the user table -- for the
     listed item rows only (``lgc_spmm_rows_split``; SCORED_ITEM_ROWS_ONLY); every other row of the result is left
     uninitialised.
+
+    ``reduced`` (``PropGraph.reduced()``, K >= 2): the middle user tables x_1 .. x_{K-1}[users] are consumed by the next
+    layer's item step only, so the users L with few entries never get a row there.  With H the kept users and
+    G_L = R_L^T R_L,   x_l[items] = R_H^T x_{l-1}[H] + G_L x_{l-2}[items]   for l >= 2.  The tables stay allocated as
+    without it and the reduced operators work on the views t[offset:] (kept user h = row h, item i = row n_h + i = row
+    split + i of t), so full and reduced operators address the same item blocks and only the tail of a middle table is
+    ever touched.  Order of the additions of an item row, fixed: (G_L x (+ mix)) + sweep sum -- the G_L launch writes the
+    row (with ``mix`` as its epilogue row in the last layer of the uniform-alpha shortcut), the kept users' item step adds
+    its sum to it (r = the row itself, b = 1: each lane reads the elements it then writes).  Layer 1's item step, the
+    last user step and both listed-rows launches are the full operators, unchanged; with listed item rows the user step
+    of layer K - 1 is the full one too, because that launch gathers every user row.
     """
     k = len(alphas) - 1
     if k == 0:
@@ -117,6 +128,30 @@ def bipartite_sum(user_op: Operator, item_op: Operator, split: int, x0: Tensor, 
     x0 = x0.contiguous()
     n = x0.size(0)
     tables = [x0]                                     # x_0 .. x_K (x_K: item rows only)
+    red = reduced if k >= 2 else None
+    rows_items_only = final_rows is not None and SCORED_ITEM_ROWS_ONLY and item_op.listed_rows_pay(final_rows.numel()) \
+        if red is not None else False
+
+    def user_step(layer: int, x: Tensor, out_t: Tensor) -> None:
+        """x_layer[users] for a middle layer: the kept users only, unless the next launch reads every user row."""
+        if red is None or (rows_items_only and layer == k - 1):
+            user_op.apply(x, out_t)
+        elif red.user_op_h is not None:
+            red.user_op_h.apply(x[red.offset:], out_t[red.offset:])
+
+    def item_step(layer: int, out_t: Tensor, a: float = 1.0, r: Optional[Tensor] = None) -> None:
+        """out_t[items] = a * x_layer[items] (+ r[items]) for layer >= 2 on the reduced operators."""
+        o = red.offset
+        y = out_t[o:]
+        have = r is not None
+        if red.gram_op is not None:
+            red.gram_op.apply(tables[layer - 2][o:], y, a=a, r=r[o:] if have else None, b=1.0 if have else 0.0)
+        elif have:
+            _native.lincomb(out_t[split:], [(1.0, r[split:])])
+        else:
+            out_t[split:].zero_()
+        if red.item_op_h is not None:
+            red.item_op_h.apply(tables[layer - 1][o:], y, a=a, r=y, b=1.0)
     # The reference's alpha is 1 / (K + 1) for every layer (src/lightgcn.py:75-79).  Then sum_{l<K} alpha_l x_l[items] IS
     # the table the last user step gathers, so the last item step adds it as its epilogue row and writes the item block
     # of the result directly: one lgc_lincomb and the K-th item table less, the same sums in the same order
@@ -128,8 +163,11 @@ def bipartite_sum(user_op: Operator, item_op: Operator, split: int, x0: Tensor, 
         with _HopSpan():
             nxt = scratch_table(x0)
             if layer < k:
-                item_op.apply(tables[-1], nxt)                                  # x_l[items]
-                user_op.apply(tables[-1], nxt)                                  # x_l[users]
+                if red is None or layer == 1:
+                    item_op.apply(tables[-1], nxt)                              # x_l[items]
+                else:
+                    item_step(layer, nxt)
+                user_step(layer, tables[-1], nxt)                               # x_l[users]
                 tables.append(nxt)
             else:
                 out = torch.empty_like(x0)
@@ -149,9 +187,15 @@ def bipartite_sum(user_op: Operator, item_op: Operator, split: int, x0: Tensor, 
                 elif uniform:
                     mix = nxt                                                   # item rows: sum_l alpha_l x_{l-1}
                     _native.lincomb(mix[split:], [(alphas[l], tables[l - 1][split:]) for l in range(1, k + 1)])
-                    item_op.apply(tables[-1], out, a=alphas[k], r=mix, b=1.0)   # out[items] = mix + alpha_K x_K[items]
+                    if red is None:
+                        item_op.apply(tables[-1], out, a=alphas[k], r=mix, b=1.0)   # out[items] = mix + alpha_K x_K[items]
+                    else:
+                        item_step(k, out, a=alphas[k], r=mix)
                 else:
-                    item_op.apply(tables[-1], nxt)                              # x_K[items]
+                    if red is None:
+                        item_op.apply(tables[-1], nxt)                          # x_K[items]
+                    else:
+                        item_step(k, nxt)
                     tables.append(nxt)
                     mix = scratch_table(x0)
                     _native.lincomb(mix[split:], [(alphas[l], tables[l - 1][split:]) for l in range(1, k + 1)])
@@ -166,7 +210,8 @@ def bipartite_sum(user_op: Operator, item_op: Operator, split: int, x0: Tensor, 
 def _layer_sum(graph: PropGraph, x: Tensor, alphas: tuple, transpose: bool, final_rows: Optional[Tensor] = None) -> Tensor:
     if USE_BIPARTITE and graph.split is not None and len(alphas) - 1 <= _native.MAX_TERMS - 1:
         user_op, item_op = graph.halves(transpose)
-        return bipartite_sum(user_op, item_op, graph.split, x, alphas, final_rows if SCORED_ROWS_ONLY else None)
+        return bipartite_sum(user_op, item_op, graph.split, x, alphas, final_rows if SCORED_ROWS_ONLY else None,
+                             reduced=graph.reduced(transpose) if len(alphas) > 2 else None)
     return horner_hops(graph.transpose_op if transpose else graph.forward_op, x, alphas)
 
 

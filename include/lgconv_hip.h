@@ -733,6 +733,55 @@ int lgc_sample_triples(const int64_t *users, int64_t n,
                        int64_t n_users, int64_t n_items, uint64_t seed, uint64_t step,
                        int64_t *pos_out, int64_t *neg_out, int32_t *status, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Middle-hop reduction of a user|item graph (an addition to ABI 14: exports only).
+ *
+ * Between two item steps of the layer loop (src/lightgcn.py:96 called K times) the user table is only a relay:
+ * x_{l+1}[items] = R^T (R x_{l-1}[items]).  A user u with few entries costs a row store and as many gathers from the big
+ * user table as from the small item table; taking the users L = {u : its row has <= max_deg entries AND <= max_deg item
+ * rows name it} out of the CSR and keeping their two-step paths as  G_L = R_L^T R_L  (item x item, sparse) gives
+ *     R^T R = R_H^T R_H + G_L
+ * with H the kept users.  G_L depends on the graph and its values only: built once, beside the tile classes and the sweep
+ * plan.  Both counts are taken because the edge list is never assumed structurally symmetric.
+ *
+ * Compact numbering: kept users keep their relative order as rows 0 .. n_kept-1, item i (node split + i) is row and
+ * column n_kept + i; with offset = split - n_kept, row r of a table view that starts at row `offset` of a full table is
+ * the compact node r, and the item rows sit where the full operators address them.
+ *
+ *   lgc_reduce_count      user_map (int32 [split]): new id of a kept user, -1 of an eliminated one; totals (int64 [4],
+ *                         device) = {n_kept, entries of the kept user rows, entries of the whole reduced CSR, expanded
+ *                         (item, item) pairs}.  Leaves prefix sums in `workspace` (>= lgc_reduce_workspace_bytes(n_nodes,
+ *                         n_edges), 256-byte aligned), which the other calls read: keep it untouched until they returned.
+ *                         The caller reads the totals back (the one sync) and sizes the outputs from them.
+ *   lgc_reduce_fill       the reduced CSR: rowptr_out int32 [n_kept + n_items + 1], entries_out [n_out = totals[2]].  User
+ *                         rows hold their entries with the columns renumbered, item rows only their entries on kept users;
+ *                         values are bit-identical copies and the entry order inside a row is preserved.
+ *   lgc_reduce_gram_count expands every entry (i, u) of an item row with u eliminated by u's row into keys (i, j) and fp64
+ *                         products A[i, u] * A[u, j], sorts them (one stable 64-bit radix sort) and counts the distinct
+ *                         keys: *total (int64, device) = nnz(G_L).  gram_workspace >= lgc_reduce_gram_workspace_bytes(n_pairs)
+ *                         (0 = does not fit), n_pairs = totals[3]; n_pairs >= 2^31 - 1: LGC_E_RANGE -- run without elimination.
+ *   lgc_reduce_gram_fill  G_L as a CSR over the same numbering: rowptr_out int32 [n_kept + n_items + 1] (user rows empty),
+ *                         entries_out [n_out = *total], columns ascending within a row, diagonal included; each value the
+ *                         fp64 sum of its products in expansion order (CSR order of the item entries, then of the user's
+ *                         row), rounded once to fp32.  No float atomics: two builds of one input are bit-identical.
+ * Argument errors come back before anything is enqueued: LGC_E_INVAL (null pointer, negative size, split outside (0, n_nodes),
+ * n_out outside its range), LGC_E_RANGE, LGC_E_WORKSPACE, LGC_E_ALIGN.  rowptr / entries are read on trust like every
+ * CSR the library built itself; an entry whose column is on the wrong side of the split is dropped.
+ * ------------------------------------------------------------------------------------- */
+size_t lgc_reduce_workspace_bytes(int64_t n_nodes, int64_t n_edges);
+int lgc_reduce_count(const int32_t *rowptr, const lgc_entry *entries, int64_t n_nodes, int64_t n_edges, int64_t split,
+                     int32_t max_deg, void *workspace, size_t workspace_bytes, int32_t *user_map, int64_t *totals,
+                     void *stream);
+int lgc_reduce_fill(const int32_t *rowptr, const lgc_entry *entries, int64_t n_nodes, int64_t n_edges, int64_t split,
+                    const void *workspace, const int32_t *user_map, int64_t n_kept, int64_t n_out, int32_t *rowptr_out,
+                    lgc_entry *entries_out, void *stream);
+size_t lgc_reduce_gram_workspace_bytes(int64_t n_pairs);
+int lgc_reduce_gram_count(const int32_t *rowptr, const lgc_entry *entries, int64_t n_nodes, int64_t n_edges, int64_t split,
+                          const void *workspace, int64_t n_pairs, void *gram_workspace, size_t gram_workspace_bytes,
+                          int64_t *total, void *stream);
+int lgc_reduce_gram_fill(const void *gram_workspace, int64_t n_pairs, int64_t n_kept, int64_t n_items, int64_t n_out,
+                         int32_t *rowptr_out, lgc_entry *entries_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
