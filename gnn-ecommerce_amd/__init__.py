@@ -8,6 +8,7 @@ The directory is called ``gnn-ecommerce_amd`` (not an importable name); ``import
 resolves to it through the shim package of that name at the repository root.
 """
 from . import _native
+from .explain import Attribution, attribute
 from .foldin import SessionLists, fold_in, fold_table
 from .graph import PropGraph, build_row_plan, clear_cache, get_graph
 from .lgconv import LGConv
@@ -23,4 +24,4 @@ __all__ = ["LightGCN", "BPRLoss", "LGConv", "PropGraph", "get_graph", "clear_cac
            "propagate_sum", "hop", "pair_dot", "check_index_status", "TripleSampler", "regularization_loss", "PartitionedTrainer", "_native",
            "SeenLists", "PositiveLists", "score_rows", "recommend_topk", "hop_distances", "shortest_paths", "paths_frame", "compute_paths",
            "rank_metrics", "evaluate_ranking", "overlap_items", "metrics_frame", "RankingResult",
-           "SessionLists", "fold_table", "fold_in"]
+           "SessionLists", "fold_table", "fold_in", "Attribution", "attribute"]

@@ -68,6 +68,18 @@ def route_name(code: int) -> str:
     return ROUTES[code & ~ROUTE_WT_STORE] + ("+wt" if code & ROUTE_WT_STORE else "")
 
 
+class AttrArgsC(Structure):
+    """lgc_attr_args"""
+    _fields_ = [("list_ptr", c_void_p), ("list_items", c_void_p), ("list_weight", c_void_p), ("item_dis", c_void_p),
+                ("rowptr", c_void_p), ("entries", c_void_p), ("row_ids", c_void_p), ("n_graph_rows", c_int64),
+                ("col_base", c_int64), ("n_rows", c_int64), ("fold", c_void_p), ("items", c_void_p), ("fold_stride", c_int64),
+                ("item_stride", c_int64), ("n_items", c_int64), ("init_rows", c_void_p), ("init", c_void_p),
+                ("init_stride", c_int64), ("n_init_rows", c_int64), ("targets", c_void_p), ("target_stride", c_int64),
+                ("contrib_ptr", c_void_p), ("contrib", c_void_p), ("base", c_void_p), ("total", c_void_p),
+                ("top_pos", c_void_p), ("top_item", c_void_p), ("top_value", c_void_p), ("status", c_void_p),
+                ("a0", c_float), ("normalize", c_int32), ("n_targets", c_int32), ("top_m", c_int32), ("dim", c_int32)]
+
+
 EXCHANGE_FN = CFUNCTYPE(c_int, c_void_p, c_int64, c_int64, c_int32, c_void_p, c_void_p)   # lgc_exchange_fn
 
 
@@ -173,6 +185,7 @@ SIGNATURES = {
     "lgc_reduce_gram_count": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_size_t,
                                       c_void_p, c_void_p]),
     "lgc_reduce_gram_fill": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
+    "lgc_attribute": (c_int, [POINTER(AttrArgsC), c_void_p]),
 }
 
 
@@ -238,6 +251,8 @@ SEED_MAX = 8192        # LGC_SEED_MAX: ids one lgc_seed_prepare launch sorts
 RM_PRECISION, RM_RECALL, RM_NDCG, RM_AP, RM_RR, RM_HIT, RM_COUNT = range(7)
 RM_MAX_CUTOFFS = 8
 COLUMN_SUMS_MAX = 64
+ATTR_MAX_TARGETS = 64  # LGC_ATTR_MAX_TARGETS: target columns of one lgc_attribute launch
+ATTR_MAX_TOP = 8       # LGC_ATTR_MAX_TOP
 
 
 def lincomb(y: torch.Tensor, terms) -> torch.Tensor:

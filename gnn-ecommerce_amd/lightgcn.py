@@ -11,7 +11,8 @@ src/inference_lightgcn.py and torchserve/lightgcn_handler.py run unchanged
 hit rate and coverage at several cutoffs from the same single ranking pass; ``recommendation_paths`` is one too: hop
 distances and shortest paths from users to their recommended items (src/inference_lightgcn.py:85-119); ``embed_sessions`` and
 ``recommend_sessions`` answer for nodes outside the table -- new visitors, known users with a fresh list -- from their
-interaction lists (``foldin``).  What changes is underneath: propagation is the HIP CSR-SpMM with
+interaction lists (``foldin``); ``explain_topk`` and ``explain_sessions`` split every recommended item's score over the user's
+own items (``explain``).  What changes is underneath: propagation is the HIP CSR-SpMM with
 the layer sum fused (``propagate.propagate_sum``) and pair scoring is one gather-dot kernel.
 """
 from __future__ import annotations
@@ -24,6 +25,7 @@ from torch import Tensor
 from torch.nn.modules.loss import _Loss
 
 from . import _native
+from .explain import Attribution, attribute
 from .foldin import SessionLists, fold_in, fold_table
 from .graph import get_graph
 from .lgconv import LGConv
@@ -300,6 +302,71 @@ class LightGCN(torch.nn.Module):
         item_t = self._serving_embedding(edge_index, edge_weight).detach()[int(n_users):]
         sel = torch.arange(rows.size(0), dtype=torch.int64, device=rows.device)
         return recommend_topk(rows, sel, item_t, sessions.mask(mask), k, workspace_bytes, return_values)
+
+    # -- which of the user's own items produced a recommendation ---------------------------------
+    def _explain_tables(self, edge_index, edge_weight, n_users, n_items, top_items):
+        """(graph, fold table, served item rows, targets int64 [rows, k] on the device) for the two methods below."""
+        w = self.embedding.weight
+        _native.require_device(w, "LightGCN.embedding.weight")
+        normalize = self.convs[0].normalize if self.num_layers > 0 else True
+        graph = get_graph(edge_index, edge_weight, self.num_nodes, normalize)
+        n_users, n_items = int(n_users), int(n_items)
+        if graph.split != n_users or n_users + n_items != self.num_nodes:
+            raise ValueError(f"fold-in needs the user|item graph split at n_users: split {graph.split}, n_users {n_users}, "
+                             f"n_items {n_items}, {self.num_nodes} nodes")
+        fold = fold_table(self, graph)
+        item_t = self._serving_embedding(edge_index, edge_weight).detach()[n_users:]
+        targets = top_items if torch.is_tensor(top_items) else torch.as_tensor(top_items, dtype=torch.int64)
+        if targets.dim() != 2:
+            raise ValueError("top_items must be [rows, k] item indices")
+        targets = targets.to(device=w.device, dtype=torch.int64).contiguous()
+        return graph, fold, item_t, targets
+
+    def explain_topk(self, edge_index, edge_weight, n_users, n_items, users, top_items, m: int = 3,
+                     full: bool = False) -> Attribution:
+        """For trained ``users`` and their recommended ``top_items`` (``recommend_topk``'s item indices, int64
+        ``[len(users), k]``): every score ``<e_u, E[t]>`` split over the user's own edge list -- ``base`` (the share of
+        the user's layer-0 row), ``total`` (base + all contributions = the score, to rounding) and per recommended item
+        the ``m`` items of the user's list that contributed most (``top_pos`` the position in the user's CSR row,
+        ``top_item``, ``top_value``); with ``full`` every contribution (``contrib``, ``contrib_ptr``; sizing it is the one
+        host sync).  The attribution is of the raw, UNMASKED score: ``recommendK`` zeroes a seen item's score rather than
+        removing it, so a seen item's explanation is of the score before the mask.  See ``explain.attribute``."""
+        graph, fold, item_t, targets = self._explain_tables(edge_index, edge_weight, n_users, n_items, top_items)
+        n_users = int(n_users)
+        ids = users if torch.is_tensor(users) else torch.as_tensor(list(users), dtype=torch.int64)
+        ids = ids.reshape(-1).to(device=fold.device, dtype=torch.int64).contiguous()
+        op = graph.forward_op
+        contrib_ptr = None
+        if full:                                             # row lengths -> first entry slot of every row, on the device
+            safe = ids.clamp(0, n_users - 1)
+            counts = (op.rowptr[safe + 1] - op.rowptr[safe]).to(torch.int64)
+            counts = torch.where((ids >= 0) & (ids < n_users), counts, torch.zeros_like(counts))
+            contrib_ptr = torch.zeros(ids.numel() + 1, dtype=torch.int64, device=ids.device)
+            contrib_ptr[1:] = torch.cumsum(counts, 0)
+        return attribute(fold, item_t, targets, rowptr=op.rowptr[:n_users + 1], entries=op.entries, row_ids=ids,
+                         col_base=n_users, contrib_ptr=contrib_ptr, init_table=self.embedding.weight.detach()[:n_users],
+                         init_rows=ids, a0=self._alphas()[0], m=m, full=full)
+
+    def explain_sessions(self, edge_index, edge_weight, n_users, n_items, sessions: SessionLists, top_items, init_users=None,
+                         m: int = 3, full: bool = False) -> Attribution:
+        """The same for interaction lists (``embed_sessions``' arguments): the scores of ``recommend_sessions``' rows
+        split over each session's own list, with fold-in's coefficients.  The attribution is of the raw, UNMASKED
+        score: a session item zeroed by the mask is explained by its score before the mask."""
+        graph, fold, item_t, targets = self._explain_tables(edge_index, edge_weight, n_users, n_items, top_items)
+        n_users = int(n_users)
+        sessions.validate(int(n_items))
+        init_table = init_rows = None
+        if init_users is not None:
+            if not torch.is_tensor(init_users):
+                ids = [int(u) for u in init_users]
+                if any(u < -1 or u >= n_users for u in ids):
+                    raise ValueError(f"init_users must be -1 or lie in [0, {n_users})")
+                init_users = torch.tensor(ids, dtype=torch.int64)
+            init_rows = init_users.reshape(-1).to(device=fold.device, dtype=torch.int64).contiguous()
+            init_table = self.embedding.weight.detach()[:n_users]
+        return attribute(fold, item_t, targets, sessions=sessions, item_dis=graph.dis[n_users:] if graph.normalize else None,
+                         normalize=graph.normalize, init_table=init_table, init_rows=init_rows, a0=self._alphas()[0], m=m,
+                         full=full)
 
     def link_pred_loss(self, pred: Tensor, edge_label: Tensor, **kwargs) -> Tensor:
         return torch.nn.BCEWithLogitsLoss(**kwargs)(pred, edge_label.to(pred.dtype))

@@ -12,7 +12,12 @@ returns what upstream returns, ``[{'items': [[k item indices], ...]}]``.  What d
   * ``inference`` also answers for visitors the model was not trained on: next to a plain user id a request element may be
     ``{"items": [...], "weights": [...] (optional), "user": id (optional)}`` -- the items the visitor looked at, put in
     the cart or bought (relabelled item indices, as the answers), upstream's event weights, and for a known user with a
-    fresh list the user whose trained layer-0 row to start from (``LightGCN.recommend_sessions``, fold-in).
+    fresh list the user whose trained layer-0 row to start from (``LightGCN.recommend_sessions``, fold-in);
+  * a body ``{"requests": [...], "explain": m}`` (``requests`` = what the body is otherwise, ``1 <= m <= 8``) is answered
+    with ``{"items": [...], "because": [...]}``: the same items, and for recommended item j of request element p
+    ``because[p][j] = {"base": float, "score": float, "items": [[item, contribution], ...]}`` -- the m items of the
+    visitor's own list that contributed most to that item's raw (unmasked) score (``LightGCN.explain_topk`` /
+    ``explain_sessions``, score attribution).
 """
 from __future__ import annotations
 
@@ -125,7 +130,52 @@ class RecommendHandler:
                 raise ValueError(f"request element {pos}: expected a user id or a dict with 'items', got {type(el).__name__}")
         return id_pos, ids, session_pos, lists, init_users
 
+    def parse_explain(self, body):
+        """``(requests, m)`` of a body ``{"requests": [...], "explain": m}``; anything else raises ValueError."""
+        unknown = set(body) - {"requests", "explain"}
+        if unknown or "requests" not in body or "explain" not in body:
+            raise ValueError(f"request body: expected 'requests' and 'explain', got {sorted(map(str, body))}")
+        requests, m = body["requests"], body["explain"]
+        if not isinstance(requests, (list, tuple)):
+            raise ValueError("request body: 'requests' must be a list of user ids and / or dicts with 'items'")
+        if isinstance(m, bool) or not isinstance(m, int) or not 1 <= m <= _native.ATTR_MAX_TOP:
+            raise ValueError(f"request body: 'explain' must be an integer in [1, {_native.ATTR_MAX_TOP}]")
+        return list(requests), m
+
+    def inference_explained(self, data, m: int):
+        """The answer of ``inference(data)`` plus, per recommended item, the ``m`` items of the visitor's own list that
+        contributed most to its score.  The scores explained are the raw ones: a seen item that the mask zeroed is
+        explained by its score before the mask."""
+        if any(isinstance(el, dict) for el in data):
+            id_pos, ids, session_pos, lists, init_users = self.parse_sessions(data)
+        else:                                                # ids alone: whatever the plain path takes (int(u))
+            id_pos, ids, session_pos, lists, init_users = list(range(len(data))), [int(u) for u in data], [], [], []
+        if not data:
+            return {"items": [], "because": []}
+        answers = self.inference(data)["items"]
+        because = [None] * len(data)
+
+        def rows_of(got, positions):
+            base, total = got.base.cpu().tolist(), got.total.cpu().tolist()
+            item, value = got.top_item.cpu().tolist(), got.top_value.cpu().tolist()
+            for r, pos in enumerate(positions):
+                because[pos] = [{"base": base[r][j], "score": total[r][j],
+                                 "items": [[i, v] for i, v in zip(item[r][j], value[r][j]) if i >= 0]}
+                                for j in range(len(answers[pos]))]
+        with torch.no_grad():
+            if ids:
+                top = torch.tensor([answers[pos] for pos in id_pos], dtype=torch.int64)
+                rows_of(self.model.explain_topk(self.graph, None, self.n_users, self.n_items, ids, top, m), id_pos)
+            if lists:
+                sessions = SessionLists.from_lists(lists, self.device).validate(self.n_items, "request")
+                top = torch.tensor([answers[pos] for pos in session_pos], dtype=torch.int64)
+                rows_of(self.model.explain_sessions(self.graph, None, self.n_users, self.n_items, sessions, top,
+                                                    init_users if any(u >= 0 for u in init_users) else None, m), session_pos)
+        return {"items": answers, "because": because}
+
     def inference(self, data, *args, **kwargs):
+        if isinstance(data, dict):
+            return self.inference_explained(*self.parse_explain(data))
         if any(isinstance(el, dict) for el in data):
             return self._inference_sessions(data)
         users = [int(u) for u in data]

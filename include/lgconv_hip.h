@@ -782,6 +782,81 @@ int lgc_reduce_gram_count(const int32_t *rowptr, const lgc_entry *entries, int64
 int lgc_reduce_gram_fill(const void *gram_workspace, int64_t n_pairs, int64_t n_kept, int64_t n_items, int64_t n_out,
                          int32_t *rowptr_out, lgc_entry *entries_out, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Score attribution (an addition to ABI 14: exports only): which of a row's own items produced a recommendation.
+ * Upstream's inference script stops at path lengths (src/inference_lightgcn.py:85-119).  Fold-in's line
+ *     e_u = a0 * z_u + sum_k c_k * F[i_k]
+ * dotted with a served item row E[t] splits every score additively over the row's list:
+ *     score(u, t) = a0 <z_u, E[t]>  +  sum_k c_k <F[i_k], E[t]>  =  base[t] + sum_k contrib[k, t]
+ * exactly (to rounding) for a session (c_k = lgc_fold_in's coefficient) and for a trained user (c_k = the value stored in
+ * the user's row of the forward CSR, whose columns are the item nodes).  One launch, one workgroup per request row.
+ *
+ * The lists, in exactly ONE of two forms (LGC_E_INVAL for both or neither; the pointers of the other form NULL):
+ *   session  list_ptr int64 [n_rows + 1], list_items int64, list_weight fp32 or NULL, item_dis, normalize: lgc_fold_in's
+ *            arguments, and c_k with lgc_fold_in's arithmetic bit for bit (sequential fp32 degree in list order, correctly
+ *            rounded 1 / sqrt with inf -> 0, (item_dis * w) * d left to right; normalize = 0: c_k = w_k).  An item outside
+ *            [0, n_items) is left out of the degree, contributes nothing and sets LGC_ST_INDEX_OOB
+ *   graph    rowptr int32, entries, row_ids int64 [n_rows], n_graph_rows, col_base: request row r is row row_ids[r] of the
+ *            CSR, item index = col - col_base, c_k = val_k unchanged.  A row id outside [0, n_graph_rows) sets the status
+ *            bit and every output of its row is the "nothing" value; a column outside [col_base, col_base + n_items) is
+ *            skipped and flagged
+ * Tables: fold (lgc_fold_in's F) and items (the served item rows E), fp32 [n_items, dim], row strides >= dim; init_rows /
+ * init / init_stride / n_init_rows / a0 as in lgc_fold_in (-1 = no row, any other bad id is flagged and adds nothing);
+ * targets int64 [n_rows, n_targets], rows target_stride apart: item indices, typically a row of lgc_mask_topk's output;
+ * -1 = "no target" silently, any other value outside [0, n_items) sets the status bit, both give "nothing" in that column.
+ * 1 <= n_targets <= LGC_ATTR_MAX_TARGETS, 0 <= top_m <= LGC_ATTR_MAX_TOP (LGC_E_RANGE beyond); dim as lgc_dim_ok.  Every
+ * index is range-checked before an address is formed from it; lists and the CSR are read on trust.
+ *
+ * Outputs, each may be NULL but not all (top_m = 0 counts as no top output):
+ *   contrib    fp32, ragged, with contrib_ptr int64 [n_rows + 1] = the first entry slot of each row (session form: list_ptr
+ *              itself will do; graph form: the prefix sum of the row lengths): entry j of row r, target t goes to
+ *              contrib[(contrib_ptr[r] + j) * n_targets + t]; at most contrib_ptr[r + 1] - contrib_ptr[r] entries of a
+ *              row are written; a skipped entry writes +0
+ *   base       fp32 [n_rows, n_targets] = a0 * dot(z, E[t]), +0 without an init row
+ *   total      fp32 [n_rows, n_targets] = the contributions that count added SEQUENTIALLY IN LIST ORDER from +0, base last
+ *   top_pos int32, top_item int64, top_value fp32, all [n_rows, n_targets, top_m]: the m contributions that rank first in
+ *              lgc_mask_topk's total order on the value (NaN first, +inf, finite descending with -0 = +0, -inf), equal
+ *              keys by ascending list position; top_pos counts skipped entries, which take no part; a repeated item
+ *              stays two entries; unused places hold -1 / -1 / +0
+ * "Nothing" value of a column or row: base = total = +0, top -1 / -1 / +0, contrib +0.
+ * Arithmetic: dot(a, b) is lgc_score_rows' chain -- fused multiply-adds over d ascending from +0, zeros past dim -- so
+ * dot(F[i], E[t]) has exactly the bits lgc_score_rows writes for that pair of rows; contrib = c_k * dot, one rounded
+ * product.  No float atomics: the same bits on every run.
+ * Errors before any launch: LGC_E_DIM; LGC_E_INVAL (a null required pointer, a negative size, n_items < 1, a stride below dim
+ * or target_stride below n_targets, both or neither list form, normalize outside {0, 1} or 1 without item_dis, init_rows
+ * without init, contrib without contrib_ptr, top_m > 0 without all three top pointers, no output at all); LGC_E_RANGE
+ * (n_targets, top_m, n_rows or n_items >= 2^31); LGC_E_ALIGN (a table that is not dword aligned).  n_rows == 0 validates,
+ * launches nothing and returns 0.
+ * ------------------------------------------------------------------------------------- */
+#define LGC_ATTR_MAX_TARGETS 64
+#define LGC_ATTR_MAX_TOP 8
+typedef struct lgc_attr_args {          /* HOST struct of device pointers and sizes */
+    const int64_t   *list_ptr, *list_items;                 /* session form */
+    const float     *list_weight, *item_dis;
+    const int32_t   *rowptr;                                /* graph form */
+    const lgc_entry *entries;
+    const int64_t   *row_ids;
+    int64_t          n_graph_rows, col_base;
+    int64_t          n_rows;
+    const float     *fold, *items;
+    int64_t          fold_stride, item_stride, n_items;
+    const int64_t   *init_rows;
+    const float     *init;
+    int64_t          init_stride, n_init_rows;
+    const int64_t   *targets;
+    int64_t          target_stride;
+    const int64_t   *contrib_ptr;
+    float           *contrib, *base, *total;
+    int32_t         *top_pos;
+    int64_t         *top_item;
+    float           *top_value;
+    int32_t         *status;
+    float            a0;
+    int32_t          normalize, n_targets, top_m, dim;
+} lgc_attr_args;
+
+int lgc_attribute(const lgc_attr_args *args, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
