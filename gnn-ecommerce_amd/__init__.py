@@ -17,6 +17,7 @@ from .paths import compute_paths, hop_distances, paths_frame, shortest_paths
 from .propagate import (PositiveLists, RankingResult, SeenLists, check_index_status, evaluate_ranking, hop, metrics_frame,
                         overlap_items, pair_dot, propagate_sum, rank_metrics, recommend_topk, score_rows)
 from .sampler import TripleSampler
+from .similar import item_neighbors, row_rnorm
 from . import ingest, serving
 from .trainer import PartitionedTrainer
 
@@ -24,4 +25,5 @@ __all__ = ["LightGCN", "BPRLoss", "LGConv", "PropGraph", "get_graph", "clear_cac
            "propagate_sum", "hop", "pair_dot", "check_index_status", "TripleSampler", "regularization_loss", "PartitionedTrainer", "_native",
            "SeenLists", "PositiveLists", "score_rows", "recommend_topk", "hop_distances", "shortest_paths", "paths_frame", "compute_paths",
            "rank_metrics", "evaluate_ranking", "overlap_items", "metrics_frame", "RankingResult",
-           "SessionLists", "fold_table", "fold_in", "Attribution", "attribute"]
+           "SessionLists", "fold_table", "fold_in", "Attribution", "attribute",
+           "item_neighbors", "row_rnorm"]

@@ -186,6 +186,10 @@ SIGNATURES = {
                                       c_void_p, c_void_p]),
     "lgc_reduce_gram_fill": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
     "lgc_attribute": (c_int, [POINTER(AttrArgsC), c_void_p]),
+    "lgc_row_rnorm": (c_int, [c_void_p, c_int64, c_int64, c_int32, c_void_p, c_void_p]),
+    "lgc_item_neighbors_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int32, c_int32]),
+    "lgc_item_neighbors": (c_int, [c_void_p, c_int64, c_int64, c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_int32, c_int32,
+                                   c_int32, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
 }
 
 
@@ -253,6 +257,7 @@ RM_MAX_CUTOFFS = 8
 COLUMN_SUMS_MAX = 64
 ATTR_MAX_TARGETS = 64  # LGC_ATTR_MAX_TARGETS: target columns of one lgc_attribute launch
 ATTR_MAX_TOP = 8       # LGC_ATTR_MAX_TOP
+NEIGHBORS_MAX_K = 64   # LGC_NEIGHBORS_MAX_K
 
 
 def lincomb(y: torch.Tensor, terms) -> torch.Tensor:

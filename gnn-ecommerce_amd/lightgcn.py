@@ -30,6 +30,7 @@ from .foldin import SessionLists, fold_in, fold_table
 from .graph import get_graph
 from .lgconv import LGConv
 from .paths import shortest_paths
+from .similar import item_neighbors
 from .propagate import (DEFAULT_WORKSPACE_BYTES, TOPK_MAX, PositiveLists, RegHook, SeenLists, bpr_loss_fused, evaluate_ranking,
                         evaluate_topk, mask_topk, pair_dot, propagate_sum, recommend_topk, regularization_through,
                         routable_index, scores_from_table)
@@ -367,6 +368,30 @@ class LightGCN(torch.nn.Module):
         return attribute(fold, item_t, targets, sessions=sessions, item_dis=graph.dis[n_users:] if graph.normalize else None,
                          normalize=graph.normalize, init_table=init_table, init_rows=init_rows, a0=self._alphas()[0], m=m,
                          full=full)
+
+    # -- which items are like this one ------------------------------------------------------------
+    def similar_items(self, edge_index, edge_weight, n_users, n_items, item_ids=None, k: int = 10, metric: str = "cosine",
+                      item_ok=None):
+        """``(index int64 [n, k], value fp32 [n, k])`` on the device: per item of ``item_ids`` (item indices WITHOUT the
+        ``n_users`` offset, as in fold-in; None = the whole catalogue in order) the ``k`` most similar other items by
+        ``metric`` ("cosine" or "dot") over the item rows of the cached serving embedding -- the table ``recommendK``
+        scores against.  ``item_ok``: bool or uint8 ``[n_items]``, items that may be returned (None = all).  The order is
+        ``recommend_topk``'s (descending, equal values by ascending index); with fewer than k other items a row ends
+        in -1 / -inf.  An id outside ``[0, n_items)`` gives such a row and raises at ``check_index_status()``.  See
+        ``similar.item_neighbors``."""
+        n_users, n_items = int(n_users), int(n_items)
+        if n_users < 0 or n_items < 1 or n_users + n_items != self.num_nodes:
+            raise ValueError(f"n_users {n_users} + n_items {n_items} != {self.num_nodes} nodes")
+        _native.require_device(self.embedding.weight, "LightGCN.embedding.weight")
+        with torch.no_grad():                                # read-only: the table recommendK keeps between requests
+            item_t = self._serving_embedding(edge_index, edge_weight).detach()[n_users:]
+        ids = None
+        if item_ids is not None:
+            ids = item_ids if torch.is_tensor(item_ids) else torch.as_tensor(list(item_ids), dtype=torch.int64)
+            ids = ids.reshape(-1).to(device=item_t.device, dtype=torch.int64).contiguous()
+        if item_ok is not None:
+            item_ok = torch.as_tensor(item_ok).to(device=item_t.device).contiguous()
+        return item_neighbors(item_t, k, ids, metric, item_ok, True, 0)
 
     def link_pred_loss(self, pred: Tensor, edge_label: Tensor, **kwargs) -> Tensor:
         return torch.nn.BCEWithLogitsLoss(**kwargs)(pred, edge_label.to(pred.dtype))

@@ -17,7 +17,10 @@ returns what upstream returns, ``[{'items': [[k item indices], ...]}]``.  What d
     with ``{"items": [...], "because": [...]}``: the same items, and for recommended item j of request element p
     ``because[p][j] = {"base": float, "score": float, "items": [[item, contribution], ...]}`` -- the m items of the
     visitor's own list that contributed most to that item's raw (unmasked) score (``LightGCN.explain_topk`` /
-    ``explain_sessions``, score attribution).
+    ``explain_sessions``, score attribution);
+  * a body ``{"similar": [item ids], "k": int (optional, 1 .. 64, default 20), "metric": "cosine" | "dot" (optional)}`` asks
+    about ITEMS: it is answered with ``{"items": [[...]], "scores": [[...]]}``, per asked-about item the most similar other
+    items of the catalogue and their similarities, best first (``LightGCN.similar_items``).
 """
 from __future__ import annotations
 
@@ -31,6 +34,7 @@ from .foldin import SessionLists
 from .graph import PropGraph
 from .lightgcn import LightGCN
 from .propagate import SeenLists
+from .similar import METRICS
 
 GRAPH_FILE = "graph.safetensors"
 
@@ -142,6 +146,35 @@ class RecommendHandler:
             raise ValueError(f"request body: 'explain' must be an integer in [1, {_native.ATTR_MAX_TOP}]")
         return list(requests), m
 
+    def parse_similar(self, body):
+        """``(item ids, k, metric)`` of a body ``{"similar": [...], "k": optional, "metric": optional}``.  A malformed body
+        raises ValueError, an item id outside ``[0, n_items)`` IndexError."""
+        unknown = set(body) - {"similar", "k", "metric"}
+        if unknown or "similar" not in body:
+            raise ValueError(f"request body: expected 'similar' and optionally 'k', 'metric'; got {sorted(map(str, body))}")
+        ids, k, metric = body["similar"], body.get("k", self.k), body.get("metric", "cosine")
+        if not isinstance(ids, (list, tuple)) or any(isinstance(i, bool) or not isinstance(i, int) for i in ids):
+            raise ValueError("request body: 'similar' must be a list of item indices")
+        if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= _native.NEIGHBORS_MAX_K:
+            raise ValueError(f"request body: 'k' must be an integer in [1, {_native.NEIGHBORS_MAX_K}]")
+        if not isinstance(metric, str) or metric not in METRICS:
+            raise ValueError(f"request body: 'metric' must be one of {list(METRICS)}")
+        if any(i < 0 or i >= self.n_items for i in ids):
+            raise IndexError(f"item index outside [0, {self.n_items})")
+        return list(ids), k, metric
+
+    def inference_similar(self, ids, k: int, metric: str):
+        """Per asked-about item the ``k`` most similar other items and their similarities, best first; places that no
+        item fills (a catalogue of fewer than k + 1 items) are dropped."""
+        if not ids:
+            return {"items": [], "scores": []}
+        with torch.no_grad():
+            index, value = self.model.similar_items(self.graph, None, self.n_users, self.n_items, ids, k, metric)
+        index, value = index.cpu().tolist(), value.cpu().tolist()
+        keep = [[j for j, i in enumerate(row) if i >= 0] for row in index]
+        return {"items": [[row[j] for j in js] for row, js in zip(index, keep)],
+                "scores": [[row[j] for j in js] for row, js in zip(value, keep)]}
+
     def inference_explained(self, data, m: int):
         """The answer of ``inference(data)`` plus, per recommended item, the ``m`` items of the visitor's own list that
         contributed most to its score.  The scores explained are the raw ones: a seen item that the mask zeroed is
@@ -175,6 +208,8 @@ class RecommendHandler:
 
     def inference(self, data, *args, **kwargs):
         if isinstance(data, dict):
+            if "similar" in data:
+                return self.inference_similar(*self.parse_similar(data))
             return self.inference_explained(*self.parse_explain(data))
         if any(isinstance(el, dict) for el in data):
             return self._inference_sessions(data)

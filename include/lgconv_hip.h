@@ -857,6 +857,59 @@ typedef struct lgc_attr_args {          /* HOST struct of device pointers and si
 
 int lgc_attribute(const lgc_attr_args *args, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Similar items (an addition to ABI 14: exports only): "which items are like this one?" -- the k nearest rows of the item
+ * table by dot product or cosine, for a product page's row of similar products, for deduplication and for diversity passes.
+ * Upstream answers questions about users only (src/lightgcn.py:165-177).  Scoring runs on the fp32 matrix cores
+ * (v_mfma_f32_16x16x4_f32) and the selection in the same launch: no score is written to memory.
+ *
+ * lgc_row_rnorm: out[r] = 1 / sqrt(sum_d table[r, d]^2), the scale that makes the dot product a cosine.
+ *   table  fp32 [n_rows, dim], rows `stride` floats apart (>= dim); out fp32 [n_rows]
+ *   ss is ONE chain ss = fma(x_d, x_d, ss) over d ascending from +0; the square root and the division are each correctly
+ *   rounded; an infinite result becomes 0 (as lgc_build_csr's dis: a zero row is similar to nothing); NaN stays NaN.
+ *   Errors: LGC_E_DIM; LGC_E_INVAL (null pointer, negative size, stride below dim); LGC_E_RANGE (n_rows >= 2^31);
+ *   LGC_E_ALIGN (a pointer that is not dword aligned).  n_rows == 0 launches nothing.
+ *
+ * lgc_item_neighbors: per query row the k best candidates among the items.
+ *   items      fp32 [n_items, dim], rows item_stride floats apart (>= dim; columns past dim are never read); n_items >= 1
+ *   query_ids  int64 [n_queries] item indices, any order, repeats allowed; NULL = query r is item r.  An id outside
+ *              [0, n_items) sets LGC_ST_INDEX_OOB in `status` and its whole row is -1 / -inf; it is range-checked before
+ *              any address is formed from it
+ *   scale      fp32 [n_items] or NULL: s = (dot * scale[query]) * scale[item], left to right, each product rounded; with
+ *              scale = lgc_row_rnorm(items) that is the cosine, with NULL s = dot
+ *   item_ok    uint8 [n_items] or NULL: an item with item_ok[i] == 0 is never returned (it may still be asked about)
+ *   exclude_self  1: the query's own item is not a candidate; 0: it is
+ *   k          1 .. LGC_NEIGHBORS_MAX_K
+ *   slices     0 .. 64: the catalogue is cut into that many ranges of item tiles, one workgroup per (tile of 64 query rows,
+ *              range), and a second small kernel merges the ranges' k best; 0 = the library chooses (the smallest count
+ *              that gives about 512 workgroups: 1 for a whole catalogue, many for a request of a few ids); a count above
+ *              the number of item tiles (128 items each) is clamped to it.  The result does not depend on it
+ *   out_index  int64 [n_queries, k]; out_value fp32 [n_queries, k] or NULL.  With fewer than k candidates the tail of the
+ *              row is -1 / -inf
+ *   workspace  device memory of at least lgc_item_neighbors_workspace_bytes(n_queries, n_items, k, slices) bytes, 8-byte
+ *              aligned; may be NULL where that is 0 (one range).  The size function returns 0 for sizes the call would
+ *              refuse and grows monotonically in n_queries, n_items, k and in slices over 1 .. 64
+ * Arithmetic: dot(q, i) is lgc_score_rows' chain -- fused multiply-adds over d ascending from +0, zeros past dim -- so it
+ * has the bits lgc_score_rows writes for the same two rows, except that a sum of -0 may come out as +0 (the width is
+ * padded with zeros to 16 columns); the order below does not tell them apart.
+ * Order: lgc_mask_topk's total order -- every NaN (either sign bit) first, then +inf, the finite values descending with
+ * -0 = +0, then -inf; equal elements by ascending index.  It is strict, so the result depends neither on the tile shape
+ * nor on the slice count nor on the order in which candidates arrive.  A NaN comes back as the quiet NaN 0x7FFFFFFF and
+ * -0 as +0.  No float atomics: the same bits on every run.
+ * Errors before any launch: LGC_E_DIM (as lgc_dim_ok); LGC_E_INVAL (a null required pointer, a negative n_queries, a
+ * stride below dim, exclude_self outside {0, 1}); LGC_E_RANGE (k outside 1 .. LGC_NEIGHBORS_MAX_K, slices outside
+ * 0 .. 64, n_items < 1, n_items or n_queries >= 2^31); LGC_E_ALIGN (items, scale or out_value not dword aligned,
+ * out_index or workspace not 8-byte aligned); LGC_E_WORKSPACE (a workspace that is too small or missing).
+ * n_queries == 0 validates, launches nothing and returns 0.
+ * ------------------------------------------------------------------------------------- */
+#define LGC_NEIGHBORS_MAX_K 64
+int lgc_row_rnorm(const float *table, int64_t stride, int64_t n_rows, int32_t dim, float *out, void *stream);
+size_t lgc_item_neighbors_workspace_bytes(int64_t n_queries, int64_t n_items, int32_t k, int32_t slices);
+int lgc_item_neighbors(const float *items, int64_t item_stride, int64_t n_items, int32_t dim,
+                       const int64_t *query_ids, int64_t n_queries, const float *scale, const uint8_t *item_ok,
+                       int32_t exclude_self, int32_t k, int32_t slices, int64_t *out_index, float *out_value,
+                       void *workspace, size_t workspace_bytes, int32_t *status, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
