@@ -190,6 +190,11 @@ SIGNATURES = {
     "lgc_item_neighbors_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int32, c_int32]),
     "lgc_item_neighbors": (c_int, [c_void_p, c_int64, c_int64, c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_int32, c_int32,
                                    c_int32, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "lgc_rerank_route": (c_int, [c_int32, c_int32]),
+    "lgc_rerank_mmr": (c_int, [c_void_p, c_int64, c_int64, c_int32, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64,
+                               c_int32, c_int32, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "lgc_list_diversity": (c_int, [c_void_p, c_int64, c_int64, c_int32, c_void_p, c_void_p, c_int64, c_int64, c_int32,
+                                   POINTER(c_int32), c_int32, c_void_p, c_int64, c_void_p, c_void_p]),
 }
 
 
@@ -258,6 +263,8 @@ COLUMN_SUMS_MAX = 64
 ATTR_MAX_TARGETS = 64  # LGC_ATTR_MAX_TARGETS: target columns of one lgc_attribute launch
 ATTR_MAX_TOP = 8       # LGC_ATTR_MAX_TOP
 NEIGHBORS_MAX_K = 64   # LGC_NEIGHBORS_MAX_K
+RERANK_MAX_CAND = 256  # LGC_RERANK_MAX_CAND
+RERANK_ROUTES = {1: "lds", 2: "global"}   # lgc_rerank_route's codes (LGC_RERANK_ROUTE_*)
 
 
 def lincomb(y: torch.Tensor, terms) -> torch.Tensor:

@@ -12,7 +12,9 @@ hit rate and coverage at several cutoffs from the same single ranking pass; ``re
 distances and shortest paths from users to their recommended items (src/inference_lightgcn.py:85-119); ``embed_sessions`` and
 ``recommend_sessions`` answer for nodes outside the table -- new visitors, known users with a fresh list -- from their
 interaction lists (``foldin``); ``explain_topk`` and ``explain_sessions`` split every recommended item's score over the user's
-own items (``explain``).  What changes is underneath: propagation is the HIP CSR-SpMM with
+own items (``explain``); ``similar_items`` answers "which items are like this one?" (``similar``); ``recommend_diverse``,
+``rerank_diverse`` and ``list_diversity`` re-rank a candidate list by greedy maximal marginal relevance and measure the
+intra-list diversity of the result (``rerank``).  What changes is underneath: propagation is the HIP CSR-SpMM with
 the layer sum fused (``propagate.propagate_sum``) and pair scoring is one gather-dot kernel.
 """
 from __future__ import annotations
@@ -31,9 +33,12 @@ from .graph import get_graph
 from .lgconv import LGConv
 from .paths import shortest_paths
 from .similar import item_neighbors
-from .propagate import (DEFAULT_WORKSPACE_BYTES, TOPK_MAX, PositiveLists, RegHook, SeenLists, bpr_loss_fused, evaluate_ranking,
-                        evaluate_topk, mask_topk, pair_dot, propagate_sum, recommend_topk, regularization_through,
-                        routable_index, scores_from_table)
+from .propagate import (DEFAULT_WORKSPACE_BYTES, TOPK_MAX, PositiveLists, RegHook, SeenLists, bpr_loss_fused, column_sums,
+                        evaluate_ranking, evaluate_topk, mask_topk, pair_dot, propagate_sum, recommend_topk,
+                        regularization_through, routable_index, scores_from_table)
+from .rerank import check_lam, list_diversity, mmr_rerank
+
+RERANK_MAX_CAND = _native.RERANK_MAX_CAND
 
 __all__ = ["LightGCN", "BPRLoss", "LGConv", "regularization_loss"]
 
@@ -392,6 +397,63 @@ class LightGCN(torch.nn.Module):
         if item_ok is not None:
             item_ok = torch.as_tensor(item_ok).to(device=item_t.device).contiguous()
         return item_neighbors(item_t, k, ids, metric, item_ok, True, 0)
+
+    # -- k recommendations that are not k variants of one product ---------------------------------
+    def _item_table(self, edge_index, edge_weight, n_users, n_items) -> Tensor:
+        """The item rows of the cached serving embedding, the table the three methods below measure similarity on."""
+        n_users, n_items = int(n_users), int(n_items)
+        if n_users < 0 or n_items < 1 or n_users + n_items != self.num_nodes:
+            raise ValueError(f"n_users {n_users} + n_items {n_items} != {self.num_nodes} nodes")
+        _native.require_device(self.embedding.weight, "LightGCN.embedding.weight")
+        with torch.no_grad():
+            return self._serving_embedding(edge_index, edge_weight).detach()[n_users:]
+
+    def recommend_diverse(self, edge_index, edge_weight, n_users, n_items, seen, users, k: int = 20, candidates: int = 100,
+                          lam: float = 0.7, metric: str = "cosine", workspace_bytes: int = DEFAULT_WORKSPACE_BYTES) -> Tensor:
+        """int64 ``[len(users), k]`` item indices on the device: the ``min(candidates, n_items)`` best of
+        ``recommend_topk`` with their masked scores, re-ranked by greedy maximal marginal relevance
+        (``rerank.mmr_rerank``): every place goes to the candidate with the best ``lam * score - (1 - lam) * (largest
+        similarity to an item already chosen)``, similarity by ``metric`` over the item rows of the serving embedding.
+        ``k <= candidates <= 256``.  With ``lam = 1`` the answer is ``recommend_topk(k)``, index for index."""
+        if isinstance(k, bool) or not isinstance(k, int) or k < 1:
+            raise ValueError("k must be a positive integer")
+        if isinstance(candidates, bool) or not isinstance(candidates, int) or not k <= candidates <= RERANK_MAX_CAND:
+            raise ValueError(f"candidates must be an integer in [k, {RERANK_MAX_CAND}], got {candidates!r} with k = {k}")
+        check_lam(lam)
+        user_t, item_t, seen, ids = self._eval_tables(edge_index, edge_weight, n_users, n_items, seen, users)
+        top, value = recommend_topk(user_t, ids, item_t, seen, min(candidates, int(n_items)), workspace_bytes, True)
+        return mmr_rerank(item_t, top, value, k, lam, metric)
+
+    def rerank_diverse(self, edge_index, edge_weight, n_users, n_items, top_items, top_values, k: int, lam: float = 0.7,
+                       metric: str = "cosine") -> Tensor:
+        """The same for any candidate list: ``top_items`` int64 ``[rows, N]`` item indices (-1 = an empty place) and
+        ``top_values`` fp32 ``[rows, N]`` their relevance -- ``recommend_topk(..., return_values=True)``'s answer or
+        ``recommend_sessions(..., return_values=True)``'s.  int64 ``[rows, k]`` on the device."""
+        item_t = self._item_table(edge_index, edge_weight, n_users, n_items)
+        cand = top_items if torch.is_tensor(top_items) else torch.as_tensor(top_items, dtype=torch.int64)
+        rel = top_values if torch.is_tensor(top_values) else torch.as_tensor(top_values, dtype=torch.float32)
+        if cand.dim() != 2 or rel.shape != cand.shape:
+            raise ValueError("top_items and top_values must be [rows, N] of the same shape")
+        cand = cand.to(device=item_t.device, dtype=torch.int64).contiguous()
+        rel = rel.to(device=item_t.device, dtype=torch.float32).contiguous()
+        return mmr_rerank(item_t, cand, rel, k, lam, metric)
+
+    def list_diversity(self, edge_index, edge_weight, n_users, n_items, top_items, ks=(5, 10, 20), metric: str = "cosine"):
+        """``(values, mean)``: the intra-list diversity of the lists ``top_items`` (int64 ``[rows, k]`` item indices) at
+        every cutoff of ``ks`` (ascending, the last <= k) -- the mean of ``1 - similarity`` over the pairs among a list's
+        first c items, float64 ``[rows, len(ks)]`` on the device (``rerank.list_diversity``) -- and its mean over the rows,
+        a tuple of Python floats (NaN where a row's is).  One host sync."""
+        item_t = self._item_table(edge_index, edge_weight, n_users, n_items)
+        lists = top_items if torch.is_tensor(top_items) else torch.as_tensor(top_items, dtype=torch.int64)
+        if lists.dim() != 2:
+            raise ValueError("top_items must be [rows, k] item indices")
+        lists = lists.to(device=item_t.device, dtype=torch.int64).contiguous()
+        values = list_diversity(item_t, lists, ks, metric)
+        n = values.size(0)
+        if n == 0:
+            return values, tuple(float("nan") for _ in range(values.size(1)))
+        sums = column_sums(values).cpu().tolist()            # the one sync
+        return values, tuple(s / n for s in sums)
 
     def link_pred_loss(self, pred: Tensor, edge_label: Tensor, **kwargs) -> Tensor:
         return torch.nn.BCEWithLogitsLoss(**kwargs)(pred, edge_label.to(pred.dtype))

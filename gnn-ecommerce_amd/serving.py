@@ -20,7 +20,12 @@ returns what upstream returns, ``[{'items': [[k item indices], ...]}]``.  What d
     ``explain_sessions``, score attribution);
   * a body ``{"similar": [item ids], "k": int (optional, 1 .. 64, default 20), "metric": "cosine" | "dot" (optional)}`` asks
     about ITEMS: it is answered with ``{"items": [[...]], "scores": [[...]]}``, per asked-about item the most similar other
-    items of the catalogue and their similarities, best first (``LightGCN.similar_items``).
+    items of the catalogue and their similarities, best first (``LightGCN.similar_items``);
+  * a body ``{"requests": [...], "diversify": lam, "candidates": N (optional), "metric": "cosine" | "dot" (optional)}``
+    (``requests`` = what the body is otherwise, ``0 <= lam <= 1``, ``k <= N <= 256``, default ``min(5 k, 256, n_items)``) is
+    answered with ``{"items": [[...]]}`` in request order: per request element its N best items re-ranked by greedy
+    maximal marginal relevance, so that the k returned are relevant AND unlike each other (``LightGCN.recommend_diverse`` /
+    ``rerank_diverse``).  ``lam = 1`` is the plain answer.  It does not combine with ``"explain"``.
 """
 from __future__ import annotations
 
@@ -34,6 +39,7 @@ from .foldin import SessionLists
 from .graph import PropGraph
 from .lightgcn import LightGCN
 from .propagate import SeenLists
+from .rerank import check_lam
 from .similar import METRICS
 
 GRAPH_FILE = "graph.safetensors"
@@ -175,6 +181,60 @@ class RecommendHandler:
         return {"items": [[row[j] for j in js] for row, js in zip(index, keep)],
                 "scores": [[row[j] for j in js] for row, js in zip(value, keep)]}
 
+    def parse_diversify(self, body):
+        """``(requests, lam, candidates, metric)`` of a body ``{"requests": [...], "diversify": lam, "candidates": optional,
+        "metric": optional}``.  A malformed body raises ValueError, a user id outside ``[0, n_users)`` IndexError."""
+        if "diversify" in body and "explain" in body:
+            raise ValueError("request body: 'diversify' and 'explain' do not combine")
+        unknown = set(body) - {"requests", "diversify", "candidates", "metric"}
+        if unknown or "requests" not in body or "diversify" not in body:
+            raise ValueError("request body: expected 'requests', 'diversify' and optionally 'candidates', 'metric'; "
+                             f"got {sorted(map(str, body))}")
+        requests, metric = body["requests"], body.get("metric", "cosine")
+        if not isinstance(requests, (list, tuple)):
+            raise ValueError("request body: 'requests' must be a list of user ids and / or dicts with 'items'")
+        try:
+            lam = check_lam(body["diversify"])
+        except ValueError as exc:
+            raise ValueError("request body: 'diversify' must be a real number in [0, 1]") from exc
+        top = _native.RERANK_MAX_CAND
+        candidates = body.get("candidates", max(self.k, min(5 * self.k, top, self.n_items)))
+        if isinstance(candidates, bool) or not isinstance(candidates, int) or not self.k <= candidates <= top:
+            raise ValueError(f"request body: 'candidates' must be an integer in [{self.k}, {top}]")
+        if not isinstance(metric, str) or metric not in METRICS:
+            raise ValueError(f"request body: 'metric' must be one of {list(METRICS)}")
+        for pos, el in enumerate(requests):
+            if isinstance(el, dict):
+                continue                                     # parse_sessions judges these
+            if isinstance(el, bool) or not isinstance(el, int):
+                raise ValueError(f"request element {pos}: expected a user id or a dict with 'items', got {type(el).__name__}")
+            if el < 0 or el >= self.n_users:
+                raise IndexError(f"user index outside [0, {self.n_users})")
+        return list(requests), lam, candidates, metric
+
+    def inference_diverse(self, data, lam: float, candidates: int, metric: str):
+        """Per request element ``k`` items out of its ``candidates`` best, chosen by greedy maximal marginal relevance: plain
+        ids through ``recommend_diverse``, interaction lists through ``recommend_sessions`` (with its masked scores) and
+        ``rerank_diverse``; the answers come back in request order."""
+        id_pos, ids, session_pos, lists, init_users = self.parse_sessions(data)
+        answers = [None] * len(data)
+        n_cand = min(candidates, self.n_items)
+        with torch.no_grad():
+            if ids:
+                top = self.model.recommend_diverse(self.graph, None, self.n_users, self.n_items, self.seen, ids, self.k,
+                                                   candidates, lam, metric)
+                for pos, row in zip(id_pos, top.cpu().tolist()):
+                    answers[pos] = row
+            if lists:
+                sessions = SessionLists.from_lists(lists, self.device).validate(self.n_items, "request")
+                top, value = self.model.recommend_sessions(self.graph, None, self.n_users, self.n_items, sessions,
+                                                           init_users if any(u >= 0 for u in init_users) else None, n_cand,
+                                                           return_values=True)
+                top = self.model.rerank_diverse(self.graph, None, self.n_users, self.n_items, top, value, self.k, lam, metric)
+                for pos, row in zip(session_pos, top.cpu().tolist()):
+                    answers[pos] = row
+        return {"items": answers}
+
     def inference_explained(self, data, m: int):
         """The answer of ``inference(data)`` plus, per recommended item, the ``m`` items of the visitor's own list that
         contributed most to its score.  The scores explained are the raw ones: a seen item that the mask zeroed is
@@ -210,6 +270,8 @@ class RecommendHandler:
         if isinstance(data, dict):
             if "similar" in data:
                 return self.inference_similar(*self.parse_similar(data))
+            if "diversify" in data:
+                return self.inference_diverse(*self.parse_diversify(data))
             return self.inference_explained(*self.parse_explain(data))
         if any(isinstance(el, dict) for el in data):
             return self._inference_sessions(data)

@@ -910,6 +910,71 @@ int lgc_item_neighbors(const float *items, int64_t item_stride, int64_t n_items,
                        int32_t exclude_self, int32_t k, int32_t slices, int64_t *out_index, float *out_value,
                        void *workspace, size_t workspace_bytes, int32_t *status, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Diversified re-ranking (an addition to ABI 14: exports only): "give me k recommendations that are not k variants of one
+ * product" -- greedy maximal marginal relevance (MMR, Carbonell & Goldstein 1998) over a candidate list, and the
+ * intra-list diversity that judges the result.  Upstream ranks by score alone (src/lightgcn.py:175-177).  One launch, one
+ * wavefront per row; the n_cand x n_cand similarity matrix of a list is never formed: k - 1 columns of it are.
+ *
+ * lgc_rerank_mmr: out of the n_cand candidates of every row, k in the order the greedy rule chooses them.
+ *   items, item_stride, n_items, dim, scale   as lgc_item_neighbors (scale fp32 [n_items] or NULL)
+ *   cand       int64 [n_rows, n_cand], rows cand_stride apart: item indices WITHOUT the n_users offset -- a row of
+ *              lgc_mask_topk or lgc_item_neighbors.  -1 is an empty position and is skipped silently; any other id outside
+ *              [0, n_items) is range-checked before an address is formed from it, skipped, and sets LGC_ST_INDEX_OOB.  A
+ *              repeated id is two candidates: positions are what is chosen
+ *   rel        fp32 [n_rows, n_cand], rows rel_stride apart: the relevance of each candidate, computed by the caller (the
+ *              masked score: for recommendK's multiplicative mask a seen item is a candidate of relevance 0)
+ *   n_cand     1 .. LGC_RERANK_MAX_CAND;  k  1 .. n_cand;  lambda in [0, 1]: 1 = relevance alone, 0 = diversity alone
+ *   out_index  int64 [n_rows, k]: the items in the order chosen;  out_pos int32 [n_rows, k] or NULL: their positions in the
+ *              candidate row;  out_value fp32 [n_rows, k] or NULL: the objective at the moment of choice, as compared (a NaN
+ *              comes back as the quiet NaN 0x7FFFFFFF, -0 as +0).  A row with fewer than k valid positions ends in
+ *              -1 / -1 / -inf
+ * Arithmetic, bit for bit.  sim(i, j) for a remaining candidate of item i and the item j just chosen: dot(i, j) is
+ * lgc_score_rows' chain -- fused multiply-adds over d ascending from +0, zeros past dim; the products commute, so
+ * dot(i, j) = dot(j, i) -- and sim = (dot * scale[i]) * scale[j], left to right, each product rounded (lgc_item_neighbors'
+ * rule with the remaining candidate in the query's place); with scale NULL sim = dot.  With oml = 1.0f - lambda in fp32:
+ *   step 0     obj_p = lambda * rel_p for every valid position p;
+ *   after the choice of position c, every valid position p not yet chosen: the first time pen_p = sim(p, c), afterwards
+ *              pen_p = (s != s || s > pen_p) ? s : pen_p with s = sim(p, c) -- the running maximum; a NaN sticks;
+ *   step t>=1  obj_p = (lambda * rel_p) - (oml * pen_p): two products and one subtraction, each rounded, nothing fused.
+ * Every step chooses the best obj_p among the positions not yet chosen in lgc_mask_topk's total order -- every NaN first,
+ * then +inf, the finite values descending with -0 = +0, then -inf -- equal objectives by ascending POSITION.  The order is
+ * strict: the result depends on cand, rel, the item rows, scale and lambda alone, not on how positions are spread over
+ * lanes, on the route or on the run.  No float atomics.  It follows that with lambda = 1 (and finite similarities: 0 * inf is
+ * a NaN) the result is the first k positions of lgc_mask_topk's order over rel.
+ * Routes: the candidate rows are staged once in LDS where n_cand * (dim rounded up to 4 * odd floats) * 4 bytes fit 36 KiB,
+ * and read from memory at every step otherwise; lgc_rerank_route answers which (or LGC_E_DIM / LGC_E_RANGE), on the host.
+ *
+ * lgc_list_diversity: intra-list diversity of ranked lists at several cutoffs.
+ *   lists      int64 [n_rows, k], rows list_stride apart; -1 and ids out of range as above; k <= LGC_RERANK_MAX_CAND
+ *   cutoffs    int32 [n_cutoffs] on the HOST as lgc_rank_metrics takes them: 1 .. LGC_RM_MAX_CUTOFFS of them, each in 1 .. k,
+ *              strictly ascending.  Positions at and past the last cutoff are not read
+ *   out        double [n_rows, n_cutoffs], rows out_stride apart
+ * For position b, t_b = the sum of (1.0 - (double) sim(a, b)) over the valid positions a < b, taken sequentially in
+ * ascending a in float64 (sim as above with i = the earlier position a), 0 for an invalid b; S_c = the sum of t_b over
+ * b < c, sequentially in ascending b; out[r, j] = S_c / (n_c (n_c - 1) / 2) with c = cutoffs[j] and n_c the valid positions
+ * among the first c.  Fewer than two valid positions give NaN (as an empty positive list gives recall NaN).  The value at
+ * a cutoff does not depend on k or on the other cutoffs.  Column means: lgc_column_sums.
+ *
+ * Errors of both, before any launch: LGC_E_DIM (as lgc_dim_ok); LGC_E_INVAL (a null required pointer, a negative n_rows,
+ * a stride below its width, a lambda that is NaN, n_cutoffs < 1); LGC_E_RANGE (n_cand outside 1 .. LGC_RERANK_MAX_CAND, k
+ * outside 1 .. n_cand resp. 1 .. LGC_RERANK_MAX_CAND, lambda outside [0, 1], n_items < 1, n_items or n_rows >= 2^31, more
+ * than LGC_RM_MAX_CUTOFFS cutoffs, cutoffs not strictly ascending or outside 1 .. k); LGC_E_ALIGN (an fp32 or int32 pointer
+ * that is not dword aligned, an int64 or double pointer that is not 8-byte aligned).  n_rows == 0 validates, launches
+ * nothing and returns 0.
+ * ------------------------------------------------------------------------------------- */
+#define LGC_RERANK_MAX_CAND 256          /* = lgc_mask_topk's k limit: a candidate list is one of its rows */
+#define LGC_RERANK_ROUTE_LDS    1        /* the candidate rows are staged in LDS */
+#define LGC_RERANK_ROUTE_GLOBAL 2        /* they are read from memory at every step */
+int lgc_rerank_route(int32_t n_cand, int32_t dim);
+int lgc_rerank_mmr(const float *items, int64_t item_stride, int64_t n_items, int32_t dim, const float *scale,
+                   const int64_t *cand, int64_t cand_stride, const float *rel, int64_t rel_stride, int64_t n_rows,
+                   int32_t n_cand, int32_t k, float lambda, int64_t *out_index, int32_t *out_pos, float *out_value,
+                   int32_t *status, void *stream);
+int lgc_list_diversity(const float *items, int64_t item_stride, int64_t n_items, int32_t dim, const float *scale,
+                       const int64_t *lists, int64_t list_stride, int64_t n_rows, int32_t k, const int32_t *cutoffs,
+                       int32_t n_cutoffs, double *out, int64_t out_stride, int32_t *status, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
