@@ -9,7 +9,8 @@ For every width the child asserts the route ``Operator.route`` reports, compares
 and launch split the switches give) with the row-pointer path bit for bit, with and without the a / r / b epilogue,
 checks both against an fp64 host evaluation of the same CSR values, and repeats the hop on strided tables whose padding
 columns hold NaN (x, r) and a sentinel bit pattern (y).  The item half runs as a band sweep (forced on); the digests of
-its outputs go into the summary, so that the parent can compare one sweep launch with several.
+its outputs go into the summary, so that the parent can compare one sweep launch with several.  So does one named
+operator of tests/sweep_support.py, hub_and_empties under g4_small: rows of more than 32 slots and rows of none.
 """
 import argparse
 import hashlib
@@ -71,6 +72,26 @@ def bits(t):
 
 def digest(t):
     return hashlib.sha256(t.contiguous().cpu().numpy().tobytes()).hexdigest()
+
+
+def named_operator(dev, op_name="hub_and_empties", cfg_name="g4_small"):
+    """One operator of tests/sweep_support.py at every width of its configuration, checked as tests/test_sweep_gpu.py
+    checks it; the digest covers all outputs."""
+    import sweep_support as ss
+    c, cfg = ss.case(op_name), ss.CONFIGS[cfg_name]
+    G.SWEEP_CFG = dict(cfg)                       # read when the operator's plan is built, at its first hop
+    op = Operator.build(c.table_rows, c.rowptr.to(dev), c.entries.to(dev), c.row_begin, c.row_end, 32, 256, tiles=False)
+    op.sweep_cols, op.sweep_bands = (c.col_lo, c.col_hi), cfg["n_bands"]
+    h = hashlib.sha256()
+    for dim in ss.widths_of(cfg):
+        x = torch.empty((c.table_rows, dim), device=dev)
+        assert op.route(x, torch.empty_like(x)) == ss.ROUTE_OF[dim] + "+wt", (dim, op.route(x, torch.empty_like(x)))
+        for out in ss.run_and_check(op, c, dim, dev, (op_name, cfg_name)):
+            h.update(out.contiguous().cpu().numpy().tobytes())
+    plan = op._sweep[cfg["groups"]]
+    ss.assert_preconditions(op_name, cfg_name, cfg, plan.dims, {"wave_npieces": plan.wave_npieces, "multi": torch.cat(
+        [plan.multi.cpu(), plan.multi_wide.cpu()])})
+    return {f"{op_name}/{cfg_name}": {"sweep": h.hexdigest(), "sweep_waves": int(plan.dims["n_waves"])}}
 
 
 def main():
@@ -149,6 +170,7 @@ def main():
         groups = 2 if 64 < dim <= 96 else 4
         summary["widths"][str(dim)] = {"sweep": digest(y[nu:]), "sweep_epilogue": digest(ye[nu:]),
                                        "sweep_waves": int(sw._sweep[groups].dims["n_waves"])}
+    summary["operators"] = named_operator(dev)        # after the loop: the plans of `sw` are built and kept
     torch.cuda.synchronize()
     with open(args.out, "w") as f:
         json.dump(summary, f)

@@ -10,6 +10,7 @@ import pytest
 import torch
 
 from conftest import ROOT
+from sweep_support import decode_sweep as _decode_sweep
 import gnn_ecommerce_amd as lg
 from gnn_ecommerce_amd import _native, synth
 from gnn_ecommerce_amd.graph import build_row_plan
@@ -485,30 +486,6 @@ def test_purchase_lists_are_validated_before_the_kernel_indexes_them():
 # ----------------------------------------------------------------------------------------------
 # band-sweep planner (host code of the library: runs without a GPU)
 # ----------------------------------------------------------------------------------------------
-def _decode_sweep(dims, arr, row_cap):
-    """slot -> [(col, value bits)] in list order, checking the step invariants on the way."""
-    groups = dims["groups"]
-    slabs = arr["slabs"].numpy().view(np.uint32).reshape(-1, 16 * groups, 4)
-    wsp, wnp = arr["wave_slab_ptr"].numpy(), arr["wave_npieces"].numpy()
-    ps = arr["piece_slot"].numpy().reshape(-1, row_cap)
-    out = {}
-    for w in range(dims["n_waves"]):
-        assert 0 <= wnp[w] <= row_cap
-        for sb in range(wsp[w], wsp[w + 1]):
-            for s in range(32):
-                used = set()
-                for grp in range(groups):
-                    x, v = int(slabs[sb, 16 * grp + (s >> 1), 2 * (s & 1)]), int(slabs[sb, 16 * grp + (s >> 1), 2 * (s & 1) + 1])
-                    col, pc = x & 0xFFFFFF, x >> 24
-                    if col == 0xFFFFFF:                                  # padding: dummy accumulator, value 0
-                        assert pc == row_cap and v == 0
-                        continue
-                    assert pc < wnp[w] and pc not in used                 # no two entries of a step share a piece
-                    used.add(pc)
-                    out.setdefault(int(ps[w, pc]), []).append((col, v))
-    return out
-
-
 @pytest.mark.parametrize("cfg", [dict(n_bands=8, waves_per_band_round=16, row_cap=39, piece_cap=64, lookahead=32),
                                  dict(n_bands=3, waves_per_band_round=4, row_cap=7, piece_cap=5, lookahead=4),
                                  dict(n_bands=1, waves_per_band_round=8, row_cap=200, piece_cap=1000, lookahead=64),
@@ -586,29 +563,33 @@ def test_sweep_plan_on_random_small_operators():
                    row_cap=draw(st.sampled_from([1, 2, 5, 78])), piece_cap=draw(st.sampled_from([1, 3, 64])),
                    lookahead=draw(st.sampled_from([4, 64])),
                    groups=draw(st.sampled_from([2, 4])), round_order=draw(st.sampled_from([0, 1, 2])))
-        return n_cols, cols, cfg
+        return n_cols, cols, cfg, draw(st.integers(0, 50)), draw(st.integers(0, 5))
 
     @settings(max_examples=60, deadline=None, suppress_health_check=list(HealthCheck))
     @given(cases())
     def check(case):
-        n_cols, cols, cfg = case
+        n_cols, cols, cfg, col_lo, row_begin = case
         n_rows = len(cols)
-        rowptr = torch.zeros(n_rows + 1, dtype=torch.int32)
-        rowptr[1:] = torch.cumsum(torch.tensor([len(c) for c in cols]), 0)
-        flat = [c for row in cols for c in row]
-        ne = len(flat)
-        entries = torch.zeros((max(ne, 1), 2), dtype=torch.int32)
-        if ne:
-            entries[:ne, 0] = torch.tensor(flat, dtype=torch.int32)
-            entries[:ne, 1] = torch.arange(1, ne + 1, dtype=torch.int32)          # value bits identify the entry
-        dims, arr = sweep_plan_host(rowptr, entries[:ne] if ne else entries[:0], 0, n_rows, 0, n_cols, cfg)
+        # the operator inside a larger CSR: row_begin rows of two entries before it, three rows of one entry after it
+        before, after = [[0, col_lo + n_cols + 3]] * row_begin, [[1]] * 3
+        lens = [len(c) for c in before + cols + after]
+        rowptr = torch.zeros(len(lens) + 1, dtype=torch.int32)
+        rowptr[1:] = torch.cumsum(torch.tensor(lens), 0)
+        flat = [c for row in before for c in row] + [col_lo + c for row in cols for c in row] + [c for row in after for c in row]
+        entries = torch.zeros((len(flat), 2), dtype=torch.int32)
+        entries[:, 0] = torch.tensor(flat, dtype=torch.int32)
+        entries[:, 1] = torch.arange(1, len(flat) + 1, dtype=torch.int32)             # value bits identify the entry
+        ne = sum(len(c) for c in cols)
+        row_end = row_begin + n_rows
+        dims, arr = sweep_plan_host(rowptr, entries, row_begin, row_end, col_lo, col_lo + n_cols, cfg)
         assert dims["n_entries"] == ne and dims["n_rows"] == n_rows
         got = _decode_sweep(dims, arr, cfg["row_cap"])
         multi = arr["multi"].numpy()[:n_rows]
+        assert (multi[:, 0] == np.arange(row_begin, row_end)).all()                   # absolute row numbers
         seen = 0
         for row, sb, se, _ in multi:
             mine = sorted(e for sl in range(sb, se) for e in got.get(sl, []))
-            want = sorted((int(c), int(v)) for c, v in entries[rowptr[row]:rowptr[row + 1]].tolist())
+            want = sorted((int(c), int(v)) for c, v in entries[rowptr[row]:rowptr[row + 1]].tolist())     # columns as stored
             assert mine == want
             seen += len(mine)
         assert seen == ne and sum(len(v) for v in got.values()) == ne

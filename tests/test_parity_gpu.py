@@ -14,6 +14,7 @@ import torch
 
 from conftest import golden_names, load_golden, rel_fro, t, worst_row_rel
 from tests_support import assert_topk_exact_up_to_ties
+from sweep_support import assert_same_plan
 from oracle import lightgcn_oracle as oracle
 
 import gnn_ecommerce_amd as lg
@@ -1570,18 +1571,7 @@ def test_device_sweep_planner_builds_the_host_planners_plan(device, cfg):
         got = G.sweep_plan_on_device(op.rowptr, op.entries, lo, hi, c0, c1, full)
         assert got is not None
         dims, arr = got
-        assert dims == want_dims, (dims, want_dims)
-        for k in ("slabs", "wave_slab_ptr", "wave_npieces", "piece_slot", "multi"):
-            a, b = arr[k].cpu(), want[k]
-            if k == "slabs":                            # (an empty plan still gets a one-element buffer)
-                a, b = a[: dims["n_slabs"] * 64 * dims["groups"]], b[: dims["n_slabs"] * 64 * dims["groups"]]
-            if k == "wave_npieces":
-                a, b = a[: dims["n_waves"]], b[: dims["n_waves"]]
-            if k == "piece_slot":                       # entries beyond a wavefront's piece count are unspecified
-                npc = want["wave_npieces"].long()
-                live = torch.arange(dims["row_cap"]).view(1, -1) < npc.view(-1, 1)
-                a, b = a.view(-1, dims["row_cap"])[live], b.view(-1, dims["row_cap"])[live]
-            assert torch.equal(a, b), (k, lo, hi)
+        assert_same_plan(dims, arr, want_dims, want, (lo, hi))      # every array; piece_slot up to each wavefront's count
     assert G.sweep_plan_on_device(op.rowptr, op.entries, nu, n, 0, nu, dict(full, piece_cap=112)) is None     # host planner's
 
 

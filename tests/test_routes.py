@@ -191,6 +191,13 @@ def test_sweep_in_several_launches_is_bit_identical_to_one(children):
         for dim, d in one.items():
             assert d["sweep_waves"] > 12, (dim, d)        # several launches at 4 and at 12 wavefronts per launch
             assert got[dim]["sweep"] == d["sweep"] and got[dim]["sweep_epilogue"] == d["sweep_epilogue"], (name, dim)
+    # a named operator of tests/sweep_support.py: rows with more than 32 slots and rows with none, in several launches
+    one = children["no_fast_tiles"][2]["operators"]
+    assert list(one) == ["hub_and_empties/g4_small"]
+    for name in SWITCH_SETS:
+        for key, d in one.items():
+            assert d["sweep_waves"] > 12, (key, d)
+            assert children[name][2]["operators"][key] == d, (name, key)
 
 
 # ----------------------------------------------------------------------------------------
