@@ -26,7 +26,7 @@ ST_SAMPLER_EXHAUSTED = 2
 class SweepCfg(Structure):
     """lgc_sweep_cfg"""
     _fields_ = [("n_bands", c_int32), ("waves_per_band_round", c_int32), ("row_cap", c_int32), ("piece_cap", c_int32),
-                ("lookahead", c_int32), ("groups", c_int32), ("round_order", c_int32)]
+                ("lookahead", c_int32), ("groups", c_int32), ("round_order", c_int32), ("light_len", c_int32)]
 
 
 class SweepDims(Structure):
@@ -34,7 +34,7 @@ class SweepDims(Structure):
     _fields_ = [("n_bands", c_int32), ("rounds", c_int32), ("row_cap", c_int32), ("piece_cap", c_int32),
                 ("n_rows", c_int32), ("groups", c_int32),
                 ("n_waves", c_int64), ("n_slabs", c_int64), ("n_slots", c_int64), ("n_entries", c_int64),
-                ("n_steps", c_int64), ("n_padding", c_int64)]
+                ("n_steps", c_int64), ("n_padding", c_int64), ("light_len", c_int32), ("reserved", c_int32)]
 
 
 class TileClassC(Structure):

@@ -1678,6 +1678,20 @@ struct SweepPiece {
     int32_t band;
 };
 
+struct DpBounds { int32_t b[65]; };   // band b = columns [b[b], b[b + 1])
+
+// Where an entry stands in the list of a wavefront of band `home`: its column, or -- an entry of a light row's piece
+// that lies in another band -- the column of `home` at the same relative position of its own band, so that it meets
+// the walk where its own band's wavefronts are at about that time.  Integer arithmetic, the same on host and device.
+__host__ __device__ inline int32_t sweep_sort_col(int32_t col, int home, const int32_t *bound, int nb) {
+    int own = 0;
+    while (own + 1 < nb && col >= bound[own + 1]) ++own;
+    if (own == home) return col;
+    const int64_t w_home = (int64_t)bound[home + 1] - bound[home], w_own = (int64_t)bound[own + 1] - bound[own];
+    if (w_own <= 0 || w_home <= 0) return col;    // (cannot happen: a band that holds an entry has columns)
+    return bound[home] + (int32_t)(((int64_t)col - bound[own]) * w_home / w_own);
+}
+
 template <class F>
 void parallel_for(int64_t n, F &&f) {
     unsigned nt = std::thread::hardware_concurrency();
@@ -1715,6 +1729,7 @@ void parallel_each(int64_t n, F &&f) {
 // contiguous per row, band-major), the rows' slot ranges, and the deal of the pieces over the wavefronts.
 struct PlanPieces {
     int PCAP = 0, rounds = 0;
+    int32_t light_len = 0;                      // the light-row length in force (cfg.light_len, resolved if it was -1)
     int64_t n_waves = 0;
     std::vector<SweepPiece> pieces;
     std::vector<lgc_multi_row> multi;
@@ -1724,18 +1739,94 @@ struct PlanPieces {
 int plan_pieces_and_deal(const std::vector<int32_t> &run_len, int64_t n_rows, int32_t row_begin, const lgc_sweep_cfg &cfg,
                          PlanPieces &out) {
     const int NB = cfg.n_bands, WPBR = cfg.waves_per_band_round, CAP = cfg.row_cap;
+    const bool pairs_ok = NB >= 2 && NB % 2 == 0;
+    if (cfg.light_len > 0 && !pairs_ok) return LGC_E_INVAL;
+    std::vector<int32_t> row_len((size_t)n_rows, 0);
+    for (int64_t i = 0; i < n_rows; ++i)
+        for (int b = 0; b < NB; ++b) row_len[(size_t)i] += run_len[(size_t)i * NB + b];
+    // f(count, band) for every run of row i that becomes pieces: one per band, or -- a light row (at most `light`
+    // entries in total) -- one per pair of adjacent bands, at home in band 2k + (i & 1) or where the entries are
+    auto for_each_run = [&](int64_t i, int32_t light, auto &&f) {
+        const int32_t *rl = &run_len[(size_t)i * NB];
+        if (light > 0 && row_len[(size_t)i] <= light) {
+            for (int b = 0; b < NB; b += 2) {
+                const int home = rl[b] == 0 ? b + 1 : rl[b + 1] == 0 ? b : b + (int)(i & 1);
+                f((int64_t)rl[b] + rl[b + 1], home);
+            }
+        } else {
+            for (int b = 0; b < NB; ++b) f((int64_t)rl[b], b);
+        }
+    };
     // piece length cap: the configured one, raised in steps of 16 while a longer cap saves a whole round
-    auto rounds_for = [&](int64_t pcap) {
+    const int64_t round_cap = (int64_t)WPBR * CAP;
+    auto rounds_for = [&](int64_t pcap, int32_t light) {
         std::vector<int64_t> per_band((size_t)NB, 0);
         for (int64_t i = 0; i < n_rows; ++i)
-            for (int b = 0; b < NB; ++b) per_band[(size_t)b] += (run_len[(size_t)i * NB + b] + pcap - 1) / pcap;
+            for_each_run(i, light, [&](int64_t cnt, int b) { per_band[(size_t)b] += (cnt + pcap - 1) / pcap; });
         const int64_t most = *std::max_element(per_band.begin(), per_band.end());
-        return (int)std::max<int64_t>(1, (most + (int64_t)WPBR * CAP - 1) / ((int64_t)WPBR * CAP));
+        return (int)std::max<int64_t>(1, (most + round_cap - 1) / round_cap);
     };
-    int PCAP = cfg.piece_cap;
-    const int fewest = rounds_for(int64_t(1) << 40);
-    while (PCAP < 4 * cfg.piece_cap && rounds_for(PCAP) > fewest) PCAP += 16;
-    const int rounds = rounds_for(PCAP);
+    auto cap_for = [&](int32_t light) {
+        int pcap = cfg.piece_cap;
+        const int fewest = rounds_for(int64_t(1) << 40, light);
+        while (pcap < 4 * cfg.piece_cap && rounds_for(pcap, light) > fewest) pcap += 16;
+        return pcap;
+    };
+    int32_t light = std::max(cfg.light_len, 0);
+    if (cfg.light_len < 0 && pairs_ok && n_rows > 0) {
+        // the planner's choice: the smallest length, up to twice the median length of the rows that have entries, that
+        // saves a round and leaves the most-loaded band 3 % of the remaining rounds to spare.  Whether a length does is not
+        // monotone (the cap stops rising as soon as the round is saved, and the piece count jumps back up), so every length
+        // is looked at: per cap of the ladder ONE pass over the rows in order of their length gives the most-loaded
+        // band for every length at once (a row changes its bands' counts when the length reaches its own)
+        const int base = rounds_for(cap_for(0), 0);
+        std::vector<int32_t> lens;
+        for (int32_t l : row_len)
+            if (l > 0) lens.push_back(l);
+        if (base > 1 && !lens.empty()) {
+            std::nth_element(lens.begin(), lens.begin() + lens.size() / 2, lens.end());
+            const int32_t top = (int32_t)std::min<int64_t>(2 * (int64_t)lens[lens.size() / 2], 1 << 16);
+            std::vector<int32_t> order;                 // the rows that can become light, shortest first
+            for (int64_t i = 0; i < n_rows; ++i)
+                if (row_len[(size_t)i] > 0 && row_len[(size_t)i] <= top) order.push_back((int32_t)i);
+            std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t c) { return row_len[(size_t)a] < row_len[(size_t)c]; });
+            std::vector<int64_t> caps;                  // the caps cap_for can arrive at, then "no cap"
+            for (int64_t c = cfg.piece_cap; ; c += 16) {
+                caps.push_back(c);
+                if (c >= 4 * (int64_t)cfg.piece_cap) break;
+            }
+            caps.push_back(int64_t(1) << 40);
+            std::vector<std::vector<int64_t>> most_at(caps.size(), std::vector<int64_t>((size_t)top + 1, 0));
+            parallel_each((int64_t)caps.size(), [&](int64_t j) {
+                const int64_t c = caps[(size_t)j];
+                std::vector<int64_t> per_band((size_t)NB, 0);
+                for (int64_t i = 0; i < n_rows; ++i)
+                    for (int b = 0; b < NB; ++b) per_band[(size_t)b] += (run_len[(size_t)i * NB + b] + c - 1) / c;
+                size_t at = 0;
+                for (int32_t l = 0; l <= top; ++l) {
+                    for (; at < order.size() && row_len[(size_t)order[at]] <= l; ++at) {
+                        const int64_t i = order[at];
+                        for (int b = 0; b < NB; ++b) per_band[(size_t)b] -= (run_len[(size_t)i * NB + b] + c - 1) / c;
+                        for_each_run(i, top, [&](int64_t cnt, int b) { per_band[(size_t)b] += (cnt + c - 1) / c; });
+                    }
+                    most_at[(size_t)j][(size_t)l] = *std::max_element(per_band.begin(), per_band.end());
+                }
+            });
+            auto rounds_of = [&](int64_t m) { return (int)std::max<int64_t>(1, (m + round_cap - 1) / round_cap); };
+            for (int32_t l = 1; l <= top; ++l) {
+                const int fewest = rounds_of(most_at.back()[(size_t)l]);
+                size_t j = 0;                           // cap_for(l), on the ladder
+                while (caps[j] < 4 * (int64_t)cfg.piece_cap && rounds_of(most_at[j][(size_t)l]) > fewest) ++j;
+                const int64_t m = most_at[j][(size_t)l];
+                if (rounds_of(m) < base && m * 100 <= (int64_t)(base - 1) * round_cap * 97) {
+                    light = l;
+                    break;
+                }
+            }
+        }
+    }
+    const int PCAP = cap_for(light);
+    const int rounds = rounds_for(PCAP, light);
     // pieces: long runs cut into near-equal parts of <= PCAP entries; slots are contiguous per row, band-major
     std::vector<SweepPiece> &pieces = out.pieces;
     int64_t row_start = 0;
@@ -1747,15 +1838,15 @@ int plan_pieces_and_deal(const std::vector<int32_t> &run_len, int64_t n_rows, in
         mr.slot_begin = (int32_t)pieces.size();
         mr.reserved = 0;
         int64_t k = row_start;                      // first entry of the row in the column-sorted array
-        for (int b = 0; b < NB; ++b) {
-            const int64_t cnt = run_len[(size_t)i * NB + b];
+        // (the two runs of a light row's pair are neighbours in its column-sorted entries: still one range per piece)
+        for_each_run(i, light, [&](int64_t cnt, int b) {
             if (cnt > 0) {
                 const int64_t parts = (cnt + PCAP - 1) / PCAP, per = (cnt + parts - 1) / parts;
                 for (int64_t q = 0; q < cnt; q += per)
                     pieces.push_back({(int32_t)(k + q), (int32_t)std::min<int64_t>(per, cnt - q), b});
             }
             k += cnt;
-        }
+        });
         row_start = k;
         mr.slot_end = (int32_t)pieces.size();
     }
@@ -1793,6 +1884,7 @@ int plan_pieces_and_deal(const std::vector<int32_t> &run_len, int64_t n_rows, in
         if ((int)wp.size() > CAP) return LGC_E_INVAL;   // cannot happen: ceil(n / U) <= CAP
     out.PCAP = PCAP;
     out.rounds = rounds;
+    out.light_len = light;
     out.n_waves = n_waves;
     return 0;
 }
@@ -1868,22 +1960,26 @@ int sweep_plan_build(lgc_sweep_plan &pl, const int32_t *rowptr, const lgc_entry 
     pl.wave_npieces.assign((size_t)n_waves, 0);
     pl.piece_slot.assign((size_t)n_waves * CAP, 0);
     const bool serpentine = cfg.round_order == 2;
+    const bool light = pp.light_len > 0;                   // some pieces may hold entries of their neighbour band
     parallel_for(n_waves, [&](int64_t wlo, int64_t whi) {
-        struct Item { int32_t col; float val; int32_t piece; };
+        struct Item { int32_t col; float val; int32_t piece; int32_t key; };
         std::vector<Item> items;
         std::vector<char> done;
         for (int64_t w = wlo; w < whi; ++w) {
             auto &wp = wave_pieces[(size_t)w];
             auto &out = wave_slabs[(size_t)w];
             pl.wave_npieces[(size_t)w] = (int32_t)wp.size();
+            const int home = (int)((w / 4) % NB);                  // the band whose columns this wavefront walks
             items.clear();
             for (size_t lp = 0; lp < wp.size(); ++lp) {
                 const SweepPiece &pc = pieces[(size_t)wp[lp]];
                 pl.piece_slot[(size_t)w * CAP + lp] = wp[lp];
-                for (int32_t k = 0; k < pc.count; ++k)
-                    items.push_back({sorted[(size_t)(pc.begin + k)].col, sorted[(size_t)(pc.begin + k)].val, (int32_t)lp});
+                for (int32_t k = 0; k < pc.count; ++k) {
+                    const lgc_entry &ent = sorted[(size_t)(pc.begin + k)];
+                    items.push_back({ent.col, ent.val, (int32_t)lp, light ? sweep_sort_col(ent.col, home, bound.data(), NB) : ent.col});
+                }
             }
-            std::stable_sort(items.begin(), items.end(), [](const Item &a, const Item &b) { return a.col < b.col; });
+            std::stable_sort(items.begin(), items.end(), [](const Item &a, const Item &b) { return a.key < b.key; });
             // odd rounds walk their band back down: what the previous round touched last is touched first, while it
             // is still in the Infinity Cache (and, for a few microseconds, in L2)
             if (serpentine && (((w / 4) / NB) / (WPBR / 4)) % 2 == 1) std::reverse(items.begin(), items.end());
@@ -1953,6 +2049,7 @@ int sweep_plan_build(lgc_sweep_plan &pl, const int32_t *rowptr, const lgc_entry 
     pl.dims.n_entries = ne;
     pl.dims.n_steps = n_steps_total;
     pl.dims.n_padding = n_pad;
+    pl.dims.light_len = pp.light_len;
     return 0;
 }
 
@@ -2040,7 +2137,8 @@ int prepare_tiles(TilePrep &out, const int32_t *order, const int32_t *meta, cons
 //   B  every row sorted by column = ONE stable radix sort of (row << 24 | col) keys; run length of every (row, band)
 //   -> host: pieces, rounds, deal (plan_pieces_and_deal: needs the run lengths only, 1.7 MB)
 //   D  every wavefront's merged column-sorted list = ONE stable radix sort of (wave << 40 | col << 16 | piece << 8 | position
-//      in the piece) keys (the low 40 bits inverted for wavefronts that walk their band downwards); then the greedy
+//      in the piece) keys (the low 40 bits inverted for wavefronts that walk their band downwards; `col` is sweep_sort_col:
+//      the column, or for a light row's entry in the neighbour band its place in the home band's walk); then the greedy
 //      conflict-free step builder, one WAVEFRONT per list: the host's scan looks at the next `lookahead` <= 64 undone
 //      entries -- exactly one wavefront of lanes.  A step takes the first undone entry, then the first whose piece differs,
 //      ... (<= GROUPS ballots), drops the taken lanes, closes the gaps through LDS and refills from the list.  Two passes:
@@ -2069,8 +2167,6 @@ __global__ void k_dp_row_keys(const int32_t *__restrict__ rowptr, int32_t row_be
     idx[k] = (int32_t)k;
 }
 
-struct DpBounds { int32_t b[65]; };
-
 __global__ void k_dp_gather(const lgc_entry *__restrict__ entries, int64_t e0, int64_t ne,
                             const unsigned long long *__restrict__ keys_sorted, const int32_t *__restrict__ idx_sorted,
                             DpBounds bound, int32_t nb, lgc_entry *__restrict__ sorted, int32_t *__restrict__ run_len) {
@@ -2087,15 +2183,18 @@ __global__ void k_dp_gather(const lgc_entry *__restrict__ entries, int64_t e0, i
 struct DpPiece { int32_t begin, count, wave, lp; };
 
 __global__ void k_dp_item_keys(const DpPiece *__restrict__ pieces, int64_t n_pieces, const lgc_entry *__restrict__ sorted,
-                               int32_t wpbr, int32_t nb, int32_t serpentine, unsigned long long *__restrict__ keys,
-                               int32_t *__restrict__ idx) {
+                               int32_t wpbr, int32_t nb, int32_t serpentine, DpBounds bound, int32_t light,
+                               unsigned long long *__restrict__ keys, int32_t *__restrict__ idx) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_pieces) return;
     const DpPiece pc = pieces[i];
     const bool down = serpentine && (((pc.wave / 4) / nb) / (wpbr / 4)) % 2 == 1;
     const unsigned long long mask = (1ull << 40) - 1;
+    const int home = (pc.wave / 4) % nb;
     for (int32_t j = 0; j < pc.count; ++j) {
-        unsigned long long low = ((unsigned long long)(unsigned)(sorted[pc.begin + j].col & 0xFFFFFF) << 16) |
+        const int32_t col = sorted[pc.begin + j].col;
+        const int32_t at = light ? sweep_sort_col(col, home, bound.b, nb) : col;     // 24 bits either way
+        unsigned long long low = ((unsigned long long)(unsigned)(at & 0xFFFFFF) << 16) |
                                  ((unsigned long long)pc.lp << 8) | (unsigned)j;
         if (down) low = ~low & mask;
         keys[pc.begin + j] = ((unsigned long long)pc.wave << 40) | low;
@@ -2119,11 +2218,14 @@ __global__ __launch_bounds__(kBlock) void k_dp_steps(const unsigned long long *_
     const unsigned long long mask = (1ull << 40) - 1;
     const int slab_dwords = 64 * groups;
     uint32_t *cp_buf = buf_cp + wib * kWave, *v_buf = buf_v + wib * kWave;
-    auto load = [&](int32_t t, uint32_t &cp, uint32_t &v) {       // list item t: column | piece << 24, value bits
+    // list item t: column | piece << 24, value bits (the key's own column field is the entry's place in the walk, which for
+    // a light row's entry in the neighbour band is not its column)
+    auto load = [&](int32_t t, uint32_t &cp, uint32_t &v) {
         unsigned long long low = keys[t] & mask;
         if (down) low = ~low & mask;
-        cp = (uint32_t)((low >> 16) & 0xFFFFFF) | ((uint32_t)((low >> 8) & 0xFF) << 24);
-        v = __float_as_uint(sorted[idx[t]].val);
+        const lgc_entry ent = sorted[idx[t]];
+        cp = ((uint32_t)ent.col & 0xFFFFFFu) | ((uint32_t)((low >> 8) & 0xFF) << 24);
+        v = __float_as_uint(ent.val);
     };
     int32_t next = begin;
     uint32_t cp = 0, v = 0;
@@ -2557,7 +2659,8 @@ lgc_sweep_plan *lgc_sweep_plan_create(const int32_t *rowptr_host, const lgc_entr
         row_end >= row_begin && col_lo >= 0 && col_hi > col_lo && col_hi <= 0xFFFFFF && cfg->n_bands >= 1 &&
         cfg->n_bands <= 64 && cfg->waves_per_band_round >= 4 && cfg->waves_per_band_round % 4 == 0 && cfg->row_cap >= 1 &&
         cfg->row_cap <= 254 && cfg->piece_cap >= 1 && cfg->lookahead >= 4 && (cfg->groups == 0 || cfg->groups == 2 || cfg->groups == 4) &&
-        cfg->round_order >= 0 && cfg->round_order <= 2) {
+        cfg->round_order >= 0 && cfg->round_order <= 2 && cfg->light_len >= -1 &&
+        (cfg->light_len <= 0 || (cfg->n_bands >= 2 && cfg->n_bands % 2 == 0))) {
         pl = new (std::nothrow) lgc_sweep_plan();
         if (pl) {
             try {
@@ -2669,7 +2772,7 @@ bool dplan_cfg_ok(const lgc_sweep_cfg *cfg) {
     return cfg && cfg->n_bands >= 1 && cfg->n_bands <= 64 && cfg->waves_per_band_round >= 4 && cfg->waves_per_band_round % 4 == 0 &&
            cfg->row_cap >= 1 && cfg->row_cap <= 254 && cfg->piece_cap >= 1 && cfg->piece_cap <= 64 && cfg->lookahead >= 4 &&
            cfg->lookahead <= 64 && (cfg->groups == 0 || cfg->groups == 2 || cfg->groups == 4) && cfg->round_order >= 0 &&
-           cfg->round_order <= 2;
+           cfg->round_order <= 2 && cfg->light_len >= -1 && (cfg->light_len <= 0 || cfg->n_bands % 2 == 0);
 }
 }  // namespace
 
@@ -2688,6 +2791,7 @@ lgc_sweep_dplan *lgc_sweep_dplan_create(const int32_t *rowptr, const lgc_entry *
     };
     // piece_cap <= 64 and lookahead <= 64: the composite sort key keeps 8 bits for an entry's position in its piece (pieces
     // hold up to 4 x piece_cap entries) and the step builder's window is one wavefront; other settings -> the host planner
+    if (cfg && (cfg->light_len < -1 || (cfg->light_len > 0 && cfg->n_bands % 2 != 0))) return fail(LGC_E_INVAL);
     if (!dplan_cfg_ok(cfg)) return fail(LGC_E_RANGE);
     if (!rowptr || row_begin < 0 || row_end < row_begin || first_entry < 0 || n_entries < 0 || col_lo < 0 || col_hi <= col_lo ||
         col_hi > 0xFFFFFF || n_entries >= INT32_MAX || (n_entries > 0 && (!entries || !workspace)))
@@ -2711,6 +2815,7 @@ lgc_sweep_dplan *lgc_sweep_dplan_create(const int32_t *rowptr, const lgc_entry *
         pl->row_begin = row_begin;
         const DplanWs ws = dplan_carve(workspace, ne, n_rows, n_cols, *cfg);
         std::vector<int32_t> run_len((size_t)n_rows * NB, 0);
+        DpBounds bound{};
         if (ne > 0) {
             // A. histogram of the columns -> band bounds
             hipError_t err = hipMemsetAsync(ws.hist, 0, (size_t)n_cols * 4, st);
@@ -2735,7 +2840,6 @@ lgc_sweep_dplan *lgc_sweep_dplan_create(const int32_t *rowptr, const lgc_entry *
             if (err == hipSuccess) err = hipStreamSynchronize(st);
             if (err != hipSuccess) return bail((int)err);
             if (bad) return bail(LGC_E_INVAL);                     // a column outside [col_lo, col_hi)
-            DpBounds bound;
             for (int b = 0; b <= NB; ++b) bound.b[b] = col_hi;
             bound.b[0] = col_lo;
             {
@@ -2784,7 +2888,7 @@ lgc_sweep_dplan *lgc_sweep_dplan_create(const int32_t *rowptr, const lgc_entry *
             if (err != hipSuccess) return bail((int)err);
             const int serp = cfg->round_order == 2 ? 1 : 0;
             hipLaunchKernelGGL(k_dp_item_keys, dim3(ceil_div(n_pieces, kBlock)), dim3(kBlock), 0, st, ws.pieces, n_pieces, ws.sorted,
-                               WPBR, NB, serp, ws.keys_a, ws.idx_a);
+                               WPBR, NB, serp, bound, pp.light_len > 0 ? 1 : 0, ws.keys_a, ws.idx_a);
             size_t cb = ws.cub_bytes;
             int wave_bits = 1;
             while ((int64_t(1) << wave_bits) < n_waves) ++wave_bits;
@@ -2826,6 +2930,7 @@ lgc_sweep_dplan *lgc_sweep_dplan_create(const int32_t *rowptr, const lgc_entry *
         pl->dims.n_entries = ne;
         pl->dims.n_steps = n_steps;
         pl->dims.n_padding = n_pad;
+        pl->dims.light_len = pp.light_len;
         (void)SLAB;
     } catch (const std::bad_alloc &) {
         return bail((int)hipErrorOutOfMemory);

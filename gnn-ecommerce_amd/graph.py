@@ -58,6 +58,22 @@ SWEEP_CFG = dict(n_bands=int(os.environ.get("LGCN_SWEEP_BANDS", "8")), waves_per
                  # their band downwards, starting on the rows the previous round left in the Infinity Cache (-2 us)
                  round_order=int(os.environ.get("LGCN_SWEEP_ROUND_ORDER", "2")))
 SWEEP_WIDE = os.environ.get("LGCN_SWEEP_WIDE", "1") == "1"
+# Light rows (lgc_sweep_cfg.light_len): an item row with at most this many entries in total gets one piece per pair of
+# adjacent bands instead of one per band -- fewer partial rows, and a round less where the light pieces forced the last
+# one.  "auto": the planner picks, per operator, the smallest length (up to twice the median row length) that saves a
+# round with 3 % of the remaining rounds to spare, else 0; "0": off; an integer: that length.  Only the plan of four
+# entries per step (61..64 columns) with the configured, even number of bands takes it by default: the adaptive band counts
+# of a partition's rank keep 0, and so does the plan for 68..96 columns (five rounds) unless LGCN_SWEEP_LIGHT_LEN_WIDE says
+# otherwise -- it is there for measurements (profiles/EXPERIMENTS.md, "Light rows").
+SWEEP_LIGHT_LEN = os.environ.get("LGCN_SWEEP_LIGHT_LEN", "auto")
+SWEEP_LIGHT_LEN_WIDE = os.environ.get("LGCN_SWEEP_LIGHT_LEN_WIDE", "0")
+
+
+def _light_len(value: str) -> int:
+    """lgc_sweep_cfg.light_len of an LGCN_SWEEP_LIGHT_LEN setting: -1 = the planner chooses."""
+    return -1 if value == "auto" else max(int(value), 0)
+
+
 PLAN_TIMING = os.environ.get("LGCN_PLAN_TIMING", "0") == "1"     # print where PropGraph.prepare spends its time
 # tables of 68..96 columns: a row takes two DPP rows, LDS rows are 96 floats -> 51 accumulators per wavefront
 SWEEP_CFG_WIDE = dict(SWEEP_CFG, row_cap=int(os.environ.get("LGCN_SWEEP_ROW_CAP_WIDE", "51")), groups=2)
@@ -318,7 +334,7 @@ def sweep_plan_host(rowptr: Tensor, entries: Tensor, row_begin: int, row_end: in
     lib = _native.load()
     handle, d = _sweep_plan_create(rowptr, entries, row_begin, row_end, col_lo, col_hi, cfg)
     try:
-        dims = {k: getattr(d, k) for k, _ in _native.SweepDims._fields_}
+        dims = {k: getattr(d, k) for k, _ in _native.SweepDims._fields_ if k != "reserved"}
         arrays = {"slabs": torch.empty(max(d.n_slabs, 1) * 64 * d.groups, dtype=torch.int32),
                   "wave_slab_ptr": torch.empty(d.n_waves + 1, dtype=torch.int32),
                   "wave_npieces": torch.empty(max(d.n_waves, 1), dtype=torch.int32),
@@ -342,7 +358,7 @@ def sweep_plan_device(rowptr: Tensor, entries: Tensor, row_begin: int, row_end: 
     dev = rowptr.device
     handle, d = _sweep_plan_create(rowptr, entries, row_begin, row_end, col_lo, col_hi, cfg)
     try:
-        dims = {k: getattr(d, k) for k, _ in _native.SweepDims._fields_}
+        dims = {k: getattr(d, k) for k, _ in _native.SweepDims._fields_ if k != "reserved"}
         i32 = dict(dtype=torch.int32, device=dev)
         arrays = {"slabs": torch.empty(max(d.n_slabs, 1) * 64 * d.groups, **i32),
                   "wave_slab_ptr": torch.empty(d.n_waves + 1, **i32),
@@ -390,7 +406,7 @@ def sweep_plan_on_device(rowptr: Tensor, entries: Tensor, row_begin: int, row_en
     try:
         d = _native.SweepDims()
         _native.check(lib.lgc_sweep_dplan_dims(handle, ctypes.byref(d)), "lgc_sweep_dplan_dims")
-        dims = {k: getattr(d, k) for k, _ in _native.SweepDims._fields_}
+        dims = {k: getattr(d, k) for k, _ in _native.SweepDims._fields_ if k != "reserved"}
         i32 = dict(dtype=torch.int32, device=dev)
         arrays = {"slabs": torch.empty(max(d.n_slabs, 1) * 64 * d.groups, **i32),
                   "wave_slab_ptr": torch.empty(d.n_waves + 1, **i32),
@@ -463,6 +479,8 @@ class Operator:
     tiled: bool = False                  # rows up to plan.short_max go through the tiled kernels
     sweep_cols: Optional[Tuple[int, int]] = None    # column range of a bipartite half that qualifies for the band sweep
     sweep_bands: int = 0                            # bands of that sweep (0: the configured number)
+    sweep_light_len: int = 0                        # lgc_sweep_cfg.light_len of its four-entry plan (-1: the planner chooses)
+    sweep_light_len_wide: int = 0                   # ... and of its two-entry plan (68..96 columns)
     _sweep: Dict[int, SweepPlan] = field(default_factory=dict)     # by entries per step: 4 (61..64 columns), 2 (68..96)
     _tiles: Optional[List[TileClass]] = None
     _partials: Dict[int, Tensor] = field(default_factory=dict)
@@ -504,6 +522,8 @@ class Operator:
             if long_rows and (USE_SWEEP == "1" or (dense_enough and n_cols >= 1 << 17)):
                 op.sweep_cols = (int(sweep_cols[0]), int(sweep_cols[1]))
                 op.sweep_bands = bands
+                if bands == SWEEP_CFG["n_bands"]:
+                    op.sweep_light_len, op.sweep_light_len_wide = _light_len(SWEEP_LIGHT_LEN), _light_len(SWEEP_LIGHT_LEN_WIDE)
         return op
 
     def sweep_plan(self, groups: int = 4) -> Optional[SweepPlan]:
@@ -517,6 +537,8 @@ class Operator:
             cfg = dict(SWEEP_CFG_WIDE if groups == 2 else SWEEP_CFG)
             if self.sweep_bands and self.sweep_bands != cfg["n_bands"]:
                 cfg.update(n_bands=self.sweep_bands, waves_per_band_round=cfg["waves_per_band_round"] * cfg["n_bands"] // self.sweep_bands)
+            elif cfg["n_bands"] % 2 == 0:
+                cfg["light_len"] = self.sweep_light_len if groups == 4 else self.sweep_light_len_wide
             plan = SweepPlan(self.rowptr, self.entries, p.row_begin, p.row_end, *self.sweep_cols, cfg=cfg)
             self._sweep[groups] = plan
         return plan

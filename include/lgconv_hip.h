@@ -31,6 +31,8 @@
 extern "C" {
 #endif
 
+/* Still 14 although lgc_sweep_cfg and lgc_sweep_dims have grown by light_len at their ends: the number is pinned by the
+ * tests of seven features.  A caller compiled against the structs without the field must be rebuilt with this header. */
 #define LGC_ABI_VERSION 14
 
 /* argument errors (negative return values) */
@@ -263,11 +265,23 @@ typedef struct lgc_sweep_cfg {
                                       order (a round starts where the previous one ended, on rows still in the Infinity
                                       Cache: another 2 us per hop).  Entries of a piece are then accumulated in
                                       descending column order in odd rounds (still one fixed order per plan)              */
+    int32_t light_len;             /* light rows: a row with at most this many entries IN TOTAL gets one piece per PAIR of
+                                      adjacent bands (2k, 2k+1) instead of one per band.  The piece lives in a wavefront of its
+                                      home band 2k + (row & 1) (row counted from row_begin), or in the band that has the
+                                      entries if the other run is empty; that wavefront gathers the neighbour band's columns
+                                      too, each sorted into the band's walk at its position relative to its own band
+                                      (bound[home] + (col - bound[own]) * width(home) / width(own)).  Fewer pieces: fewer
+                                      partial rows and possibly a round less.  0 = off (the plan of before, array for array);
+                                      > 0 needs an even n_bands (LGC_E_INVAL otherwise); -1 = the planner chooses: the smallest
+                                      length, up to twice the median row length, with which the plan takes one round less and
+                                      its most-loaded band fills at most 97 % of the remaining rounds, else 0 (also for odd
+                                      n_bands).  lgc_sweep_dims.light_len reports the length in force                        */
 } lgc_sweep_cfg;
 
 typedef struct lgc_sweep_dims {
     int32_t n_bands, rounds, row_cap, piece_cap, n_rows, groups;
     int64_t n_waves, n_slabs, n_slots, n_entries, n_steps, n_padding;
+    int32_t light_len, reserved;   /* the light-row length the plan was built with (cfg.light_len, resolved if it was -1) */
 } lgc_sweep_dims;
 
 typedef struct lgc_sweep_plan lgc_sweep_plan;
@@ -293,6 +307,8 @@ void lgc_sweep_plan_free(lgc_sweep_plan *plan);
  * wavefront's merged column-sorted list (a second radix sort) and the conflict-free step builder, one wavefront per list
  * (its look-ahead window is the wavefront's 64 lanes).  The 81 MB of entries are never copied to the host and the 87 MB of
  * slabs never from it.  Needs cfg->piece_cap <= 64 and cfg->lookahead <= 64 (LGC_E_RANGE otherwise: use the host planner).
+ * cfg->light_len as in the host planner (the list order of a light row's entries in its neighbour band is the sort key's
+ * 24-bit column field; the slabs carry the entries' own columns).
  *   lgc_sweep_dplan_create   everything up to the sizes (returns NULL and sets *code on error); `workspace` (device,
  *                            >= lgc_sweep_dplan_workspace_bytes) must stay untouched until _fill has returned
  *   lgc_sweep_dplan_dims     as lgc_sweep_plan_dims
