@@ -185,6 +185,11 @@ SIGNATURES = {
     "lgc_reduce_gram_count": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_size_t,
                                       c_void_p, c_void_p]),
     "lgc_reduce_gram_fill": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
+    "lgc_reduce_concat_rows": (c_int64, [c_int64, c_int64, c_int32]),
+    "lgc_reduce_concat": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int32, c_void_p,
+                                  c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "lgc_reduce_concat_host": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int32,
+                                       c_void_p, c_void_p, c_void_p, c_void_p, c_int64]),
     "lgc_attribute": (c_int, [POINTER(AttrArgsC), c_void_p]),
     "lgc_row_rnorm": (c_int, [c_void_p, c_int64, c_int64, c_int32, c_void_p, c_void_p]),
     "lgc_item_neighbors_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int32, c_int32]),

@@ -1,6 +1,7 @@
 // lgconv_reduce.hip -- middle-hop reduction of a user|item graph (include/lgconv_hip.h, lgc_reduce_*): the users with few
 // entries are taken out of the CSR and their two-step paths item -> user -> item are kept as one sparse item x item
 // operator  G_L = R_L^T R_L  instead.  One-time planning calls beside the tile classes and the sweep plan, not hop launches.
+// lgc_reduce_concat lays both out as ONE operator [R_H^T | G_L] over a column space with gaps for the item rows.
 //
 // Everything is index arithmetic plus one stable radix sort and fixed-order fp64 sums: no float atomics, the same bits on
 // every build.  Integer atomics only count (k_reduce_incount), which is order independent.
@@ -82,7 +83,7 @@ size_t gram_ws(void *base, int64_t n_pairs, GramWs *ws) {
 }
 
 // The row that holds entry e: the last r in [0, n_rows) with rowptr[r] <= e (rows without entries are stepped over).
-__device__ inline int32_t row_of_entry(const int32_t *__restrict__ rowptr, int32_t n_rows, int32_t e) {
+__host__ __device__ inline int32_t row_of_entry(const int32_t *__restrict__ rowptr, int32_t n_rows, int32_t e) {
     int32_t lo = 0, hi = n_rows;              // invariant: rowptr[lo] <= e < rowptr[hi]
     while (hi - lo > 1) {
         const int32_t mid = lo + (hi - lo) / 2;
@@ -254,6 +255,138 @@ __global__ void k_gram_fill_rowptr(const unsigned long long *__restrict__ keys, 
     rowptr_out[r] = head_scan[lo];            // lo == n_pairs: the total
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// The concatenated operator (lgc_reduce_concat, lgc_reduce_concat_host).  Every array element is one call of a function
+// below, from a kernel or from the host loop: the same arithmetic on both sides, no scan, no sort, no atomics.
+// ---------------------------------------------------------------------------------------------------------------------
+struct Concat {
+    const int32_t *rp;          // reduced CSR, compact numbering: [n_kept + n_items + 1]
+    const lgc_entry *ent;
+    const int32_t *grp;         // G_L, same numbering
+    const lgc_entry *gent;
+    int32_t n_kept, n_items, n_gaps, gap_rows, n_phys, n_gram, n_out;
+    int32_t *pos, *gap_start, *rowptr_out;
+    lgc_entry *out;
+};
+
+// Band of kept user h: where the entries of the kept user rows before it fall among n_gaps equal shares (for a
+// structurally symmetric graph these are the column counts of R_H^T: the sweep planner's own band rule).
+__host__ __device__ inline int32_t cc_band(const Concat &c, int32_t h) {
+    const int64_t ne = c.rp[c.n_kept];
+    if (ne <= 0) return 0;
+    const int64_t b = (int64_t)c.rp[h] * c.n_gaps / ne;
+    return (int32_t)(b < c.n_gaps - 1 ? b : c.n_gaps - 1);
+}
+
+// Kept users of bands 0 .. b: the first h with rp[h] * n_gaps >= ne * (b + 1) (rp does not decrease).
+__host__ __device__ inline int32_t cc_users_upto(const Concat &c, int32_t b) {
+    const int64_t ne = c.rp[c.n_kept];
+    if (b >= c.n_gaps - 1 || ne <= 0) return c.n_kept;
+    int32_t lo = 0, hi = c.n_kept;
+    while (lo < hi) {
+        const int32_t mid = lo + (hi - lo) / 2;
+        if ((int64_t)c.rp[mid] * c.n_gaps < ne * (b + 1)) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+__host__ __device__ inline int32_t cc_min(int64_t a, int64_t b) { return (int32_t)(a < b ? a : b); }
+
+// pos[h], h < n_kept; gap_start[b], b < n_gaps (index n_kept + b)
+__host__ __device__ inline void cc_layout_at(const Concat &c, int64_t t) {
+    if (t < c.n_kept) c.pos[t] = (int32_t)t + c.gap_rows * cc_band(c, (int32_t)t);
+    else if (t < (int64_t)c.n_kept + c.n_gaps) {
+        const int32_t b = (int32_t)(t - c.n_kept);
+        c.gap_start[b] = cc_users_upto(c, b) + c.gap_rows * b;
+    }
+}
+
+// rowptr_out[r], r <= n_phys + n_items.  Entries are laid out in physical row order: the kept users of band 0, the
+// one-entry rows of gap 0, the users of band 1, ... then the item rows (each: its R_H^T entries, then its G_L entries).
+__host__ __device__ inline void cc_rowptr_at(const Concat &c, int64_t r) {
+    if (r > (int64_t)c.n_phys + c.n_items) return;
+    int64_t v;
+    if (r >= c.n_phys) {
+        const int32_t i = (int32_t)(r - c.n_phys);
+        v = (int64_t)c.rp[c.n_kept] + c.n_items + (c.rp[c.n_kept + i] - c.rp[c.n_kept]) + c.grp[c.n_kept + i];
+    } else {
+        int32_t before = 0;                                             // gaps that start at or before row r
+        while (before < c.n_gaps && c.gap_start[before] <= r) ++before;
+        if (before > 0 && r < (int64_t)c.gap_start[before - 1] + c.gap_rows) {
+            const int32_t b = before - 1;
+            const int64_t j = (int64_t)b * c.gap_rows + (r - c.gap_start[b]);
+            v = (int64_t)c.rp[c.gap_start[b] - c.gap_rows * b] + cc_min(j, c.n_items);
+        } else {
+            const int32_t h = (int32_t)(r - (int64_t)c.gap_rows * before);
+            v = (int64_t)c.rp[h] + cc_min((int64_t)before * c.gap_rows, c.n_items);
+        }
+    }
+    c.rowptr_out[r] = (int32_t)v;
+}
+
+// Source element t of the four lists, in this order: the kept user rows' entries, the items (one gap row each), the
+// item rows' entries on kept users, the entries of G_L.
+__host__ __device__ inline void cc_entry_at(const Concat &c, int64_t t) {
+    const int64_t n_user = c.rp[c.n_kept], n_all = c.rp[c.n_kept + c.n_items];
+    const int64_t first_item_entry = n_user + c.n_items;                // of the output
+    int64_t dst;
+    lgc_entry en;
+    if (t < n_user) {                                                   // (h, item): the item's row moves behind the gaps
+        const int32_t h = row_of_entry(c.rp, c.n_kept, (int32_t)t);
+        en = c.ent[t];
+        en.col = c.n_phys + (en.col - c.n_kept);
+        dst = t + cc_min((int64_t)cc_band(c, h) * c.gap_rows, c.n_items);
+    } else if ((t -= n_user) < c.n_items) {                             // gap row of item t: 1.0 * the item's row
+        const int32_t b = (int32_t)(t / c.gap_rows);
+        en.col = c.n_phys + (int32_t)t;
+        en.val = 1.0f;
+        dst = (int64_t)c.rp[c.gap_start[b] - c.gap_rows * b] + t;
+    } else if ((t -= c.n_items) < n_all - n_user) {                     // (item i, h)
+        const int64_t e = n_user + t;
+        const int32_t i = row_of_entry(c.rp + c.n_kept, c.n_items, (int32_t)e);
+        en = c.ent[e];
+        en.col = c.pos[en.col];
+        dst = first_item_entry + t + c.grp[c.n_kept + i];
+    } else if ((t -= n_all - n_user) < c.n_gram) {                      // (item i, item j): column = j's gap row
+        const int32_t i = row_of_entry(c.grp + c.n_kept, c.n_items, (int32_t)t);
+        en = c.gent[t];
+        const int32_t j = en.col - c.n_kept;
+        en.col = c.gap_start[j / c.gap_rows] + j % c.gap_rows;
+        dst = first_item_entry + (c.rp[c.n_kept + i + 1] - n_user) + t;
+    } else {
+        return;
+    }
+    if (dst >= 0 && dst < c.n_out) c.out[dst] = en;
+}
+
+__global__ void k_concat_layout(Concat c) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    cc_layout_at(c, t);
+}
+__global__ void k_concat_rowptr(Concat c) {
+    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    cc_rowptr_at(c, r);
+}
+__global__ void k_concat_entries(Concat c) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t < c.n_out) cc_entry_at(c, t);
+}
+
+int concat_args(const int32_t *rowptr, const lgc_entry *entries, int64_t n_entries, const int32_t *gram_rowptr,
+                const lgc_entry *gram_entries, int64_t n_gram, int64_t n_kept, int64_t n_items, int32_t n_gaps,
+                int32_t *user_pos, int32_t *gap_start, int32_t *rowptr_out, lgc_entry *entries_out, int64_t n_out, Concat *c) {
+    if (n_entries < 0 || n_gram < 0 || n_kept < 0 || n_items < 1 || n_gaps < 1 || n_out < 0) return LGC_E_INVAL;
+    if (n_gaps > LGC_REDUCE_MAX_GAPS) return LGC_E_RANGE;
+    const int64_t gap_rows = (n_items + n_gaps - 1) / n_gaps, n_phys = n_kept + gap_rows * n_gaps;
+    if (n_phys + n_items >= INT32_MAX || n_entries + n_items + n_gram >= INT32_MAX) return LGC_E_RANGE;
+    if (!rowptr || !gram_rowptr || !gap_start || !rowptr_out || !entries_out || (n_entries > 0 && !entries) ||
+        (n_gram > 0 && !gram_entries) || (n_kept > 0 && !user_pos) || n_out != n_entries + n_items + n_gram)
+        return LGC_E_INVAL;
+    *c = Concat{rowptr, entries, gram_rowptr, gram_entries, (int32_t)n_kept, (int32_t)n_items, n_gaps, (int32_t)gap_rows,
+                (int32_t)n_phys, (int32_t)n_gram, (int32_t)n_out, user_pos, gap_start, rowptr_out, entries_out};
+    return 0;
+}
+
 int reduce_args_ok(const int32_t *rowptr, const lgc_entry *entries, int64_t n_nodes, int64_t n_edges, int64_t split) {
     if (n_nodes < 0 || n_edges < 0 || split < 0) return LGC_E_INVAL;
     if (n_nodes >= INT32_MAX || n_edges >= INT32_MAX) return LGC_E_RANGE;
@@ -380,6 +513,40 @@ int lgc_reduce_gram_fill(const void *gram_workspace, int64_t n_pairs, int64_t n_
         hipLaunchKernelGGL(k_gram_fill_entries, dim3(ceil_div(n_pairs, kBlock)), dim3(kBlock), 0, st, gw.keys_out, gw.vals_out,
                            gw.head_scan, (long long)n_pairs, (int32_t)n_kept, (int32_t)n_out, entries_out);
     return (int)hipGetLastError();
+}
+
+int64_t lgc_reduce_concat_rows(int64_t n_kept, int64_t n_items, int32_t n_gaps) {
+    if (n_kept < 0 || n_items < 1 || n_gaps < 1 || n_gaps > LGC_REDUCE_MAX_GAPS) return -1;
+    return n_kept + (n_items + n_gaps - 1) / n_gaps * n_gaps;
+}
+
+int lgc_reduce_concat(const int32_t *rowptr, const lgc_entry *entries, int64_t n_entries, const int32_t *gram_rowptr,
+                      const lgc_entry *gram_entries, int64_t n_gram, int64_t n_kept, int64_t n_items, int32_t n_gaps,
+                      int32_t *user_pos, int32_t *gap_start, int32_t *rowptr_out, lgc_entry *entries_out, int64_t n_out,
+                      void *stream_) {
+    Concat c;
+    if (const int rc = concat_args(rowptr, entries, n_entries, gram_rowptr, gram_entries, n_gram, n_kept, n_items, n_gaps,
+                                   user_pos, gap_start, rowptr_out, entries_out, n_out, &c))
+        return rc;
+    hipStream_t st = as_stream(stream_);
+    hipLaunchKernelGGL(k_concat_layout, dim3(ceil_div(n_kept + n_gaps, kBlock)), dim3(kBlock), 0, st, c);
+    hipLaunchKernelGGL(k_concat_rowptr, dim3(ceil_div((int64_t)c.n_phys + n_items + 1, kBlock)), dim3(kBlock), 0, st, c);
+    hipLaunchKernelGGL(k_concat_entries, dim3(ceil_div(n_out, kBlock)), dim3(kBlock), 0, st, c);
+    return (int)hipGetLastError();
+}
+
+int lgc_reduce_concat_host(const int32_t *rowptr, const lgc_entry *entries, int64_t n_entries, const int32_t *gram_rowptr,
+                           const lgc_entry *gram_entries, int64_t n_gram, int64_t n_kept, int64_t n_items, int32_t n_gaps,
+                           int32_t *user_pos, int32_t *gap_start, int32_t *rowptr_out, lgc_entry *entries_out, int64_t n_out) {
+    Concat c;
+    if (const int rc = concat_args(rowptr, entries, n_entries, gram_rowptr, gram_entries, n_gram, n_kept, n_items, n_gaps,
+                                   user_pos, gap_start, rowptr_out, entries_out, n_out, &c))
+        return rc;
+    if (rowptr[n_kept + n_items] != n_entries || gram_rowptr[n_kept + n_items] != n_gram) return LGC_E_INVAL;
+    for (int64_t t = 0; t < n_kept + n_gaps; ++t) cc_layout_at(c, t);
+    for (int64_t r = 0; r <= (int64_t)c.n_phys + n_items; ++r) cc_rowptr_at(c, r);
+    for (int64_t t = 0; t < n_out; ++t) cc_entry_at(c, t);
+    return 0;
 }
 
 }  // extern "C"

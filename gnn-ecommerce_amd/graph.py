@@ -20,7 +20,7 @@ from __future__ import annotations
 import os
 from collections import OrderedDict
 from dataclasses import dataclass, field
-from typing import Dict, List, Optional, Tuple
+from typing import Callable, Dict, List, Optional, Tuple
 
 import torch
 from torch import Tensor
@@ -826,6 +826,65 @@ def build_reduced_csr(rowptr: Tensor, entries: Tensor, split: int, num_nodes: in
                       gram_entries)
 
 
+# The item step of a reduced layer as ONE operator [R_H^T | G_L] (lgc_reduce_concat): the entries of G_L
+# ride in the kept users' band sweep, gathering x_{l-2}[items] from gaps inside the user part of table l-1.
+# "0": the separate G_L launch; "1": the concatenated operator wherever it can be built (G_L not empty, and at least as many
+# eliminated users as gap rows, so that the gaps fit in front of the item block); "auto": only where the concatenated
+# operator runs as a band sweep (a table of a width lgc_sweep_ok takes, a graph large enough for the sweep) -- measured on
+# the cosmetics graph with both plans: -1.6 % at D=64 / K=3 (four entries per step), -1.7 % at D=90 / K=5 (two), each beyond
+# three times the parent's spread (profiles/EXPERIMENTS.md, "Reduced layers: G_L inside the band sweep").  Through the
+# tile / chunk kernels it is correct (the tests run it there) but unmeasured, so "auto" keeps the separate launch.
+REDUCED_CONCAT = os.environ.get("LGCN_REDUCED_CONCAT", "auto")
+if REDUCED_CONCAT not in ("0", "1", "auto"):
+    raise ValueError(f"LGCN_REDUCED_CONCAT must be 0, 1 or auto, got {REDUCED_CONCAT!r}")
+
+
+@dataclass
+class ConcatCSR:
+    """What ``build_concat_csr`` returns: kept users and gaps as rows 0 .. n_phys - 1, item i as row and column n_phys + i."""
+    n_gaps: int
+    gap_rows: int
+    n_phys: int
+    user_pos: Tensor            # int32 [n_h]: physical row of kept user h
+    gap_start: Tensor           # int32 [n_gaps]: first row of gap b; item j owns row gap_start[j // gap_rows] + j % gap_rows
+    rowptr: Tensor              # int32 [n_phys + n_items + 1]
+    entries: Tensor             # int32 [nnz + n_items + nnz(G_L), 2]
+
+
+def build_concat_csr(csr: ReducedCSR, n_gaps: int, host: bool = False) -> ConcatCSR:
+    """lgc_reduce_concat on a reduced CSR and its G_L: three launches, no host sync (every size is known).  ``host``:
+    the same code on CPU tensors (lgc_reduce_concat_host)."""
+    lib = _native.load()
+    dev = csr.rowptr.device
+    if not host:
+        _native.require_device(csr.rowptr, "rowptr")
+    n_phys = int(lib.lgc_reduce_concat_rows(csr.n_h, csr.n_items, n_gaps))
+    if n_phys < 0:
+        raise ValueError(f"no concatenated layout for {csr.n_h} kept users, {csr.n_items} items and {n_gaps} gaps")
+    i32 = dict(dtype=torch.int32, device=dev)
+    n_out = csr.nnz + csr.n_items + csr.gram_nnz
+    user_pos, gap_start = torch.empty(max(csr.n_h, 1), **i32), torch.empty(n_gaps, **i32)
+    rowptr, entries = torch.empty(n_phys + csr.n_items + 1, **i32), torch.empty((n_out, 2), **i32)
+    args = (_native.ptr(csr.rowptr), _native.ptr(csr.entries) if csr.nnz else None, csr.nnz, _native.ptr(csr.gram_rowptr),
+            _native.ptr(csr.gram_entries) if csr.gram_nnz else None, csr.gram_nnz, csr.n_h, csr.n_items, n_gaps,
+            _native.ptr(user_pos), _native.ptr(gap_start), _native.ptr(rowptr), _native.ptr(entries), n_out)
+    if host:
+        _native.check(lib.lgc_reduce_concat_host(*args), "lgc_reduce_concat_host")
+    else:
+        with torch.cuda.device(dev):
+            _native.check(lib.lgc_reduce_concat(*args, _native.stream_of(dev)), "lgc_reduce_concat")
+    return ConcatCSR(n_gaps, (csr.n_items + n_gaps - 1) // n_gaps, n_phys, user_pos[:csr.n_h], gap_start, rowptr, entries)
+
+
+@dataclass
+class ConcatGraph:
+    """The two operators of a reduced layer over the physical numbering, on table views that start at row ``offset``."""
+    csr: ConcatCSR
+    offset: int
+    user_op: Operator           # kept users and gap rows: x_l[H], and x_{l-1}[items] into the gaps of table l
+    item_op: Operator           # [R_H^T | G_L]
+
+
 @dataclass
 class ReducedGraph:
     """The operators of the middle layers with the low-degree users eliminated (``PropGraph.reduced``).  All three work
@@ -837,11 +896,35 @@ class ReducedGraph:
     user_op_h: Optional[Operator]       # None when no user is kept
     item_op_h: Optional[Operator]       # None when the kept users leave the item rows empty
     gram_op: Optional[Operator]         # None when G_L is empty
+    concat_build: Optional[Callable[[], Optional[ConcatGraph]]] = None
+    concat_mode: Optional[str] = None   # forces LGCN_REDUCED_CONCAT for this graph ("0", "1", "auto"); None: the knob
+    _concat: Optional[list] = None      # [ConcatGraph or None] once built
+
+    def concat_for(self, dim: int, table_rows: int, stride: int) -> Optional[ConcatGraph]:
+        """The concatenated operators if the reduced layers of a propagation of this width run on them (module comment
+        at REDUCED_CONCAT), else None: the separate G_L launch.  ``table_rows`` / ``stride``: the middle tables' rows and row
+        stride, as Operator.apply will see them.  Built on first use."""
+        mode = self.concat_mode if self.concat_mode is not None else REDUCED_CONCAT
+        if mode == "0" or self.concat_build is None or self.gram_op is None:
+            return None
+        if mode == "auto" and (self.item_op_h is None or self.item_op_h.sweep_cols is None):
+            return None                                   # too small a graph for the band sweep: not worth the build
+        if self._concat is None:
+            self._concat = [self.concat_build()]
+        cc = self._concat[0]
+        if cc is None or mode == "1":
+            return cc
+        if cc.item_op.sweep_cols is None:
+            return None
+        return cc if sweep_choice(_native.load(), dim, max(table_rows - cc.offset, 0), stride) else None
 
     def nbytes(self) -> int:
         c = self.csr
         total = sum(t.numel() * 4 for t in (c.user_map, c.rowptr, c.entries, c.gram_rowptr, c.gram_entries))
-        for op in (self.user_op_h, self.item_op_h, self.gram_op):
+        cc = self._concat[0] if self._concat else None
+        if cc is not None:
+            total += sum(t.numel() * 4 for t in (cc.csr.user_pos, cc.csr.gap_start, cc.csr.rowptr, cc.csr.entries))
+        for op in (self.user_op_h, self.item_op_h, self.gram_op) + ((cc.user_op, cc.item_op) if cc is not None else ()):
             if op is not None:
                 total += op.plan.chunks.numel() * 4 + sum(tc.slab.numel() * 4 + tc.order.numel() * 4 + tc.meta.numel() * 4
                                                           for tc in (op._tiles or []))
@@ -998,7 +1081,20 @@ class PropGraph:
                                        sweep_cols=(0, n_h))
         if csr.gram_nnz > 0:
             gram_op = Operator.build(n_rows, csr.gram_rowptr, csr.gram_entries, n_h, n_rows, self.short_max, GRAM_CHUNK_LEN)
-        return ReducedGraph(csr, n_h, self.split - n_h, user_op_h, item_op_h, gram_op)
+
+        def concat() -> Optional[ConcatGraph]:
+            n_gaps = int(SWEEP_CFG["n_bands"])
+            n_phys = int(_native.load().lgc_reduce_concat_rows(n_h, csr.n_items, n_gaps))
+            if csr.gram_nnz == 0 or n_phys < 0 or n_phys > self.split:
+                return None                               # nothing to concatenate, or the gaps do not fit before the items
+            cc = build_concat_csr(csr, n_gaps)
+            rows = n_phys + csr.n_items
+            return ConcatGraph(cc, self.split - n_phys,
+                               Operator.build(rows, cc.rowptr, cc.entries, 0, n_phys, self.short_max, user_chunk,
+                                              sweep_cols=(n_phys, rows)),
+                               Operator.build(rows, cc.rowptr, cc.entries, n_phys, rows, self.short_max, self.chunk_len,
+                                              sweep_cols=(0, n_phys)))
+        return ReducedGraph(csr, n_h, self.split - n_h, user_op_h, item_op_h, gram_op, concat_build=concat)
 
     def prepare(self, dim: int, table_rows: Optional[int] = None, transpose: bool = False) -> "PropGraph":
         """Build, now, every work plan a propagation of width ``dim`` will use (they are otherwise built lazily inside
@@ -1012,7 +1108,11 @@ class PropGraph:
         ops = [(op, rows) for op in ops]
         red = self.reduced(transpose)
         if red is not None:                                   # the middle layers' operators work on views of rows - offset rows
-            ops += [(op, max(rows - red.offset, 0)) for op in (red.user_op_h, red.item_op_h, red.gram_op) if op is not None]
+            cc = red.concat_for(dim, rows, stride)
+            if cc is not None:
+                ops += [(cc.user_op, max(rows - cc.offset, 0)), (cc.item_op, max(rows - cc.offset, 0))]
+            else:
+                ops += [(op, max(rows - red.offset, 0)) for op in (red.user_op_h, red.item_op_h, red.gram_op) if op is not None]
         import time
         for op, rows in ops:
             t0 = time.perf_counter()

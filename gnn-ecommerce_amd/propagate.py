@@ -116,11 +116,19 @@ def bipartite_sum(user_op: Operator, item_op: Operator, split: int, x0: Tensor, 
     G_L = R_L^T R_L,   x_l[items] = R_H^T x_{l-1}[H] + G_L x_{l-2}[items]   for l >= 2.  The tables stay allocated as
     without it and the reduced operators work on the views t[offset:] (kept user h = row h, item i = row n_h + i = row
     split + i of t), so full and reduced operators address the same item blocks and only the tail of a middle table is
-    ever touched.  Order of the additions of an item row, fixed: (G_L x (+ mix)) + sweep sum -- the G_L launch writes the
-    row (with ``mix`` as its epilogue row in the last layer of the uniform-alpha shortcut), the kept users' item step adds
-    its sum to it (r = the row itself, b = 1: each lane reads the elements it then writes).  Layer 1's item step, the
-    last user step and both listed-rows launches are the full operators, unchanged; with listed item rows the user step
-    of layer K - 1 is the full one too, because that launch gathers every user row.
+    ever touched.  Layer 1's item step, the last user step and both listed-rows launches are the full operators,
+    unchanged; with listed item rows the user step of layer K - 1 is the full one too, because that launch gathers every
+    user row.
+
+    Order of the additions of an item row, fixed from run to run.  With the concatenated operator
+    (``reduced.concat_for``, LGCN_REDUCED_CONCAT) the item step of a reduced layer is ONE apply of
+    [R_H^T | G_L]: the row is  a * (sum over its pieces, the entries of G_L among them, each at its gap column's place in
+    the band walk) + r,  with r = ``mix`` in the last layer of the uniform-alpha shortcut and no epilogue row otherwise --
+    one sweep and one combine.  The entries of G_L gather x_{l-2}[items] from the gaps of table l-1, which the user step
+    of layer l-1 filled through its one-entry gap rows (bit-identical copies).  Without it (switch off, G_L empty, fewer
+    eliminated users than gap rows, or a width "auto" leaves out):  (a * G_L x (+ mix)) + a * sweep sum -- the G_L launch
+    writes the row, the kept users' item step adds its sum to it (r = the row itself, b = 1: each lane reads the elements
+    it then writes).  The two orders differ in the last bits, both inside the 1e-5 gate.
     """
     k = len(alphas) - 1
     if k == 0:
@@ -132,15 +140,25 @@ def bipartite_sum(user_op: Operator, item_op: Operator, split: int, x0: Tensor, 
     rows_items_only = final_rows is not None and SCORED_ITEM_ROWS_ONLY and item_op.listed_rows_pay(final_rows.numel()) \
         if red is not None else False
 
+    # the scratch tables' geometry decides (as Operator.apply will): rows of the full table, row stride of scratch_table
+    cc = red.concat_for(x0.size(1), n, x0.size(1) if (not PAD_INTERNAL or x0.size(1) % 32 == 0)
+                        else (x0.size(1) + 31) // 32 * 32) if red is not None else None
+
     def user_step(layer: int, x: Tensor, out_t: Tensor) -> None:
         """x_layer[users] for a middle layer: the kept users only, unless the next launch reads every user row."""
         if red is None or (rows_items_only and layer == k - 1):
             user_op.apply(x, out_t)
+        elif cc is not None:                              # ... and x_{layer-1}[items] into the gaps of out_t
+            cc.user_op.apply(x[cc.offset:], out_t[cc.offset:])
         elif red.user_op_h is not None:
             red.user_op_h.apply(x[red.offset:], out_t[red.offset:])
 
     def item_step(layer: int, out_t: Tensor, a: float = 1.0, r: Optional[Tensor] = None) -> None:
         """out_t[items] = a * x_layer[items] (+ r[items]) for layer >= 2 on the reduced operators."""
+        if cc is not None:
+            o = cc.offset
+            cc.item_op.apply(tables[layer - 1][o:], out_t[o:], a=a, r=None if r is None else r[o:], b=0.0 if r is None else 1.0)
+            return
         o = red.offset
         y = out_t[o:]
         have = r is not None

@@ -798,6 +798,38 @@ int lgc_reduce_gram_count(const int32_t *rowptr, const lgc_entry *entries, int64
 int lgc_reduce_gram_fill(const void *gram_workspace, int64_t n_pairs, int64_t n_kept, int64_t n_items, int64_t n_out,
                          int32_t *rowptr_out, lgc_entry *entries_out, void *stream);
 
+/* The concatenated operator [R_H^T | G_L] (an addition to ABI 14: exports only): the item step of a reduced layer as ONE
+ * operator, so that the entries of G_L run inside the kept users' band sweep instead of a launch of their own.  A sweep
+ * entry's column is both its place in the band walk and the table row it gathers, so the rows of x_{l-2}[items] must sit
+ * INSIDE the user part of table l-1, spread over the bands.  Physical numbering, from the outputs of lgc_reduce_fill /
+ * lgc_reduce_gram_fill (compact numbering) alone:
+ *   gap_rows = ceil(n_items / n_gaps);  n_phys = n_kept + n_gaps * gap_rows  (lgc_reduce_concat_rows);  rows 0 .. n_phys - 1
+ *   are the kept users with n_gaps gaps of gap_rows rows between them, item i is row and column n_phys + i (so a view that
+ *   starts at row split - n_phys of a full table has the item block where the full operators address it; the caller checks
+ *   n_phys <= split).  Kept user h belongs to band floor(rowptr[h] * n_gaps / rowptr[n_kept]) (at most n_gaps - 1; band 0
+ *   if the kept rows are empty) -- the share of the kept user rows' entries before it, which on a structurally symmetric
+ *   graph is the sweep planner's own band rule applied to R_H^T -- and gap b follows the users of band b:
+ *       user_pos[h]  = h + gap_rows * band(h)                                      int32 [n_kept]
+ *       gap_start[b] = (kept users of bands 0 .. b) + gap_rows * b                 int32 [n_gaps]
+ *   and item j owns row gap_start[j / gap_rows] + j % gap_rows (the last gap may keep up to n_gaps - 1 rows unused).
+ *   rowptr_out  int32 [n_phys + n_items + 1], entries_out [n_out = n_entries + n_items + n_gram]:
+ *     kept user rows   their entries in order, values bit-identical, columns moved behind the gaps;
+ *     gap row of j     ONE entry {n_phys + j, 1.0f}: the user step that writes x_l[H] thereby also writes x_{l-1}[j] into its
+ *                      gap (0 + 1.0f * v is v), and no launch is spent on filling the gaps; an unused gap row is empty;
+ *     item row i       its entries on kept users (columns user_pos[h]) followed by its entries of G_L (columns = the gap
+ *                      rows), values bit-identical.  Columns are NOT ascending within a row: the sweep planners sort.
+ * n_gaps <= LGC_REDUCE_MAX_GAPS (LGC_E_RANGE).  Three launches of index arithmetic, no scan, no sort, no atomics.
+ * lgc_reduce_concat_host is the same code on HOST arrays (every element is one call of the function the kernels call). */
+#define LGC_REDUCE_MAX_GAPS 64
+int64_t lgc_reduce_concat_rows(int64_t n_kept, int64_t n_items, int32_t n_gaps);     /* n_phys; -1 on a bad argument */
+int lgc_reduce_concat(const int32_t *rowptr, const lgc_entry *entries, int64_t n_entries, const int32_t *gram_rowptr,
+                      const lgc_entry *gram_entries, int64_t n_gram, int64_t n_kept, int64_t n_items, int32_t n_gaps,
+                      int32_t *user_pos, int32_t *gap_start, int32_t *rowptr_out, lgc_entry *entries_out, int64_t n_out,
+                      void *stream);
+int lgc_reduce_concat_host(const int32_t *rowptr, const lgc_entry *entries, int64_t n_entries, const int32_t *gram_rowptr,
+                           const lgc_entry *gram_entries, int64_t n_gram, int64_t n_kept, int64_t n_items, int32_t n_gaps,
+                           int32_t *user_pos, int32_t *gap_start, int32_t *rowptr_out, lgc_entry *entries_out, int64_t n_out);
+
 /* ---------------------------------------------------------------------------------------
  * Score attribution (an addition to ABI 14: exports only): which of a row's own items produced a recommendation.
  * Upstream's inference script stops at path lengths (src/inference_lightgcn.py:85-119).  Fold-in's line

@@ -6,8 +6,8 @@
 A numpy restatement of the planner's phases A-C (csrc/lgconv_hip.hip, plan_pieces_and_deal): bands by equal entry
 counts, one piece per (row, band) -- per (row, pair of bands) for a light row, at home in band 2k + (row & 1) or where
 the entries are -- cut at the piece cap (the configured 64 raised in steps of 16 while that saves a round, or --pcap N
-fixed), rounds filled by piece weight.  For the full item half and the reduced one (users of degree <= T eliminated,
-DESIGN section 17) and every threshold it prints
+fixed), rounds filled by piece weight.  For the full item half, the reduced one (users of degree <= T eliminated,
+DESIGN section 17), the reduced one concatenated with G_L (same section) and every threshold it prints
 
     light rows, their share of the entries, pieces, the most-loaded band, rounds, the partial rows' bytes (256 B per
     piece at D = 64) and the compulsory row fetches: distinct (executing band, round, user row) triples, i.e. how often
@@ -38,6 +38,34 @@ def item_half(user, item, n_users, max_deg):
         user, item = np.cumsum(keep)[user[sel]] - 1, item[sel]
     order = np.lexsort((user, item))
     return item[order].astype(np.int64), user[order].astype(np.int64)
+
+
+def concat_half(user, item, n_users, n_items, max_deg):
+    """(row, column, columns) of the concatenated operator [R_H^T | G_L] (lgc_reduce_concat): the kept
+    users renumbered around NB gaps of ceil(n_items / NB) rows, gap b where band b's share of R_H^T's entries ends, and the
+    pattern of G_L = R_L^T R_L with column j at item j's row inside its gap."""
+    deg = np.bincount(user, minlength=n_users)
+    row, col = item_half(user, item, n_users, max_deg)
+    n_h = int(col.max()) + 1
+    bound = bands(col, n_h)
+    gap_rows = -(-n_items // NB)
+    phys = col + gap_rows * np.searchsorted(bound[1:NB], col, side="right")
+    gap_start = bound[1:NB + 1] + gap_rows * np.arange(NB)
+    sel = (deg <= max_deg)[user]
+    u, it = user[sel], item[sel]
+    order = np.argsort(u, kind="stable")
+    u, it = u[order], it[order]
+    start = np.concatenate(([0], np.cumsum(np.bincount(u, minlength=n_users))))[u]
+    pi, pj = [], []
+    for k in range(max_deg):                     # entry (u, i) times the k-th entry of u's row
+        ok = deg[u] > k
+        pi.append(it[ok])
+        pj.append(it[start[ok] + k])
+    key = np.unique(np.concatenate(pi).astype(np.int64) * n_items + np.concatenate(pj))
+    gi, gj = key // n_items, key % n_items
+    row, col = np.concatenate((row, gi)), np.concatenate((phys, gap_start[gj // gap_rows] + gj % gap_rows))
+    order = np.lexsort((col, row))
+    return row[order], col[order], n_h + NB * gap_rows
 
 
 def bands(col, n_cols):
@@ -117,9 +145,13 @@ def main():
     print("| operator | light_len | light rows | their entries | pieces | most in a band | piece cap | rounds | partial rows "
           "| row fetches | per used row |")
     print("|---|---|---|---|---|---|---|---|---|---|---|")
-    for name, max_deg in (("reduced item half (T=%d)" % args.max_deg, args.max_deg), ("full item half", 0)):
-        row, col = item_half(g.user, g.item, g.n_users, max_deg)
-        n_cols = int(col.max()) + 1
+    for name, max_deg in (("concatenated [R_H^T | G_L] (T=%d)" % args.max_deg, -args.max_deg),
+                          ("reduced item half (T=%d)" % args.max_deg, args.max_deg), ("full item half", 0)):
+        if max_deg < 0:
+            row, col, n_cols = concat_half(g.user, g.item, g.n_users, g.n_items, -max_deg)
+        else:
+            row, col = item_half(g.user, g.item, g.n_users, max_deg)
+            n_cols = int(col.max()) + 1
         bound = bands(col, n_cols)
         band = np.searchsorted(bound[1:NB], col, side="right")
         run_len = np.bincount(row * NB + band, minlength=g.n_items * NB).reshape(g.n_items, NB)
