@@ -43,7 +43,7 @@ extern "C" {
 #define LGC_E_ALIGN      (-5)  /* pointer / stride alignment requirement violated           */
 
 /* bits OR-ed into device status words */
-#define LGC_ST_INDEX_OOB 1     /* an index was outside [0, n_nodes); that element was skipped */
+#define LGC_ST_INDEX_OOB 1     /* an index was outside [0, n_nodes); that element was skipped (lgc_build_csr parks it) */
 
 /* One adjacency entry as the kernels read it: 8 bytes, {source column, fp32 value}. */
 typedef struct lgc_entry {
@@ -96,6 +96,19 @@ int lgc_dim_ok(int32_t dim);
  *   entries     out lgc_entry [n_edges]; inside a row the entries keep the edge order
  *   edge_val    out fp32 [n_edges] in ORIGINAL edge order, or NULL
  *   deg_out, dis_out  out fp32 [n_nodes] or NULL
+ *   status      device int32; bits are OR-ed into it (atomicOr), never written: other bits survive
+ *
+ * Arithmetic, bit for bit (tests/test_build_gpu.py): deg = ((0 + w_0) + w_1) + ... over a row's edges in edge
+ * order; dis = 1 / sqrt(deg) with both steps correctly rounded; val = fl(fl(dis[j] * w) * dis[i]); with
+ * normalize = 0 the weight's bits come through unchanged (NaN payloads, -0.0).  fp32 denormals are kept, in the
+ * weights and in deg, as on the host.
+ *
+ * An edge with an endpoint outside [0, n_nodes) -- tested as int64 before any address is formed from it: 2^32 is out
+ * of range, not node 0 -- sets LGC_ST_INDEX_OOB in `status` and is PARKED, not dropped: it is counted in row 0, keeps
+ * its place in edge order there, and its entry is {col 0, val +0.0}, its edge_val +0.0.  Its weight still enters
+ * deg[0]: once the bit is set, deg[0], dis[0] and the values of the edges that touch node 0 are unspecified (every
+ * other row, entry and value is what the build without the bad edges gives), and a caller is expected to discard the
+ * build, as PropGraph does (IndexError).
  * ------------------------------------------------------------------------------------- */
 size_t lgc_build_workspace_bytes(int64_t n_nodes, int64_t n_edges);
 
