@@ -131,6 +131,8 @@ SIGNATURES = {
     "lgc_apply_route": (c_int, [POINTER(OperatorC), c_int64, c_int64, c_int64, c_int64, c_int32]),
     "lgc_apply": (c_int, [POINTER(OperatorC), c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_float, c_float,
                           c_int32, c_void_p]),
+    "lgc_apply2": (c_int, [POINTER(OperatorC), c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64,
+                           c_float, c_float, c_float, c_int32, c_void_p]),
     "lgc_hop_exchange": (c_int, [POINTER(OperatorC), POINTER(OperatorC), c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p,
                                  c_int64, c_float, c_float, c_int32, c_int32, c_int32, c_int32, EXCHANGE_FN, c_void_p, c_void_p]),
     "lgc_segment_sum": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_void_p, c_int64, c_int64, c_int32,

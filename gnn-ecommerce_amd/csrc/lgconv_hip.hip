@@ -1433,6 +1433,108 @@ __global__ __launch_bounds__(kBlock) void k_sweep_combine(SpmmArgs p, const lgc_
     finish_row<VEC, SpmmArgs>(p, mr.row, c0, acc, rv);
 }
 
+// k_sweep_combine with a second epilogue row (lgc_apply2):  y = (b2 * r2 + b * r) + a * acc  -- the association of
+// lgc_lincomb over the terms (b2, r2), (b, r), (a, sum), so that an item step can write a layer sum in its place.  A kernel
+// of its own, the same sums in the same order, so that k_sweep_combine keeps its code for every other layer; r is required.
+struct EpilogueRow2 {
+    const float *r2;
+    int64_t r2_stride;
+    float b2;
+};
+
+template <int VEC>
+__device__ __forceinline__ void finish_row2(const SpmmArgs &p, const EpilogueRow2 &q, int64_t row, int c0, Acc<VEC> acc,
+                                            const Acc<VEC> &rv, const Acc<VEC> &r2v) {
+    if (p.a != 1.0f) {
+#pragma unroll
+        for (int i = 0; i < VEC; ++i) acc.v[i] = __fmul_rn(p.a, acc.v[i]);
+    }
+#pragma unroll
+    for (int i = 0; i < VEC; ++i)
+        acc.v[i] = __fadd_rn(__fadd_rn(__fmul_rn(q.b2, r2v.v[i]), __fmul_rn(p.b, rv.v[i])), acc.v[i]);
+    store_out<VEC, SpmmArgs>(p, row, c0, acc);
+}
+
+template <int VEC>
+__global__ __launch_bounds__(kBlock) void k_sweep_combine2(SpmmArgs p, const lgc_multi_row *__restrict__ wide, int32_t n_wide,
+                                                          const lgc_multi_row *__restrict__ multi, int32_t n_multi,
+                                                          const float *__restrict__ partials, EpilogueRow2 q) {
+    __shared__ float wave_sum[(kBlock / kWave) * 256];
+    const int lane = threadIdx.x & (kWave - 1);
+    const int wv = threadIdx.x / kWave;
+    const int groups = kWave / p.lpr;
+    const int g = lane / p.lpr;
+    const int l = lane - g * p.lpr;
+    const int c0 = lane_column<VEC>(l, p.dim);
+    const float *pb = partials + c0;
+    if ((int32_t)blockIdx.x < n_wide) {
+        const lgc_multi_row mr = wide[blockIdx.x];
+        const bool active = g < groups;
+        const int units = (kBlock / kWave) * groups;
+        Acc<VEC> acc;
+        acc.zero();
+        if (active) {
+            int32_t s = mr.slot_begin + wv * groups + g;
+            for (; s + 3 * units < mr.slot_end; s += 4 * units) {
+                Acc<VEC> t0 = load_row<VEC>(pb + (int64_t)s * p.dim);
+                Acc<VEC> t1 = load_row<VEC>(pb + (int64_t)(s + units) * p.dim);
+                Acc<VEC> t2 = load_row<VEC>(pb + (int64_t)(s + 2 * units) * p.dim);
+                Acc<VEC> t3 = load_row<VEC>(pb + (int64_t)(s + 3 * units) * p.dim);
+#pragma unroll
+                for (int i = 0; i < VEC; ++i)
+                    acc.v[i] = __fadd_rn(__fadd_rn(__fadd_rn(__fadd_rn(acc.v[i], t0.v[i]), t1.v[i]), t2.v[i]), t3.v[i]);
+            }
+            for (; s < mr.slot_end; s += units) {
+                Acc<VEC> t0 = load_row<VEC>(pb + (int64_t)s * p.dim);
+#pragma unroll
+                for (int i = 0; i < VEC; ++i) acc.v[i] = __fadd_rn(acc.v[i], t0.v[i]);
+            }
+        }
+        for (int j = 1; j < groups; ++j) {   // every lane executes the shuffles; group 0 keeps the wave's sum
+#pragma unroll
+            for (int i = 0; i < VEC; ++i) {
+                float other = __shfl_down(acc.v[i], j * p.lpr);
+                if (g == 0) acc.v[i] = __fadd_rn(acc.v[i], other);
+            }
+        }
+        if (active && g == 0) {
+#pragma unroll
+            for (int i = 0; i < VEC; ++i) wave_sum[wv * 256 + l * VEC + i] = acc.v[i];
+        }
+        __syncthreads();
+        if (wv == 0 && active && g == 0) {
+            for (int o = 1; o < kBlock / kWave; ++o) {
+#pragma unroll
+                for (int i = 0; i < VEC; ++i) acc.v[i] = __fadd_rn(acc.v[i], wave_sum[o * 256 + l * VEC + i]);
+            }
+            const Acc<VEC> r2v = load_row<VEC>(q.r2 + (int64_t)mr.row * q.r2_stride + c0);
+            const Acc<VEC> rv = load_row<VEC>(p.r + (int64_t)mr.row * p.r_stride + c0);
+            finish_row2<VEC>(p, q, mr.row, c0, acc, rv, r2v);
+        }
+        return;
+    }
+    const int64_t m = (((int64_t)blockIdx.x - n_wide) * (kBlock / kWave) + wv) * groups + g;
+    if (g >= groups || m >= n_multi) return;
+    const lgc_multi_row mr = multi[m];
+    Acc<VEC> acc;
+    acc.zero();
+    const Acc<VEC> r2v = load_row<VEC>(q.r2 + (int64_t)mr.row * q.r2_stride + c0);   // both rows requested before the slots
+    const Acc<VEC> rv = load_row<VEC>(p.r + (int64_t)mr.row * p.r_stride + c0);
+    for (int32_t s = mr.slot_begin; s < mr.slot_end; s += 8) {
+        Acc<VEC> t[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            t[j].zero();
+            if (s + j < mr.slot_end) t[j] = load_row<VEC>(pb + (int64_t)(s + j) * p.dim);
+        }
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+#pragma unroll
+            for (int i = 0; i < VEC; ++i) acc.v[i] = __fadd_rn(acc.v[i], t[j].v[i]);
+    }
+    finish_row2<VEC>(p, q, mr.row, c0, acc, rv, r2v);
+}
+
 // The columns of the listed rows get `value` in `mark` (lgc_seed_mark): the rows the seeded pull has to look at.  Every
 // writer stores the same byte, so the order does not matter.
 __global__ void k_seed_mark(const int32_t *__restrict__ rowptr, const lgc_entry *__restrict__ entries, int32_t row_begin,
@@ -2995,11 +3097,15 @@ int lgc_sweep_ok(int32_t dim, int64_t table_rows, int64_t x_stride) {
     return groups != 0 && sweep_table_ok(dim, table_rows, x_stride) ? groups : 0;
 }
 
-int lgc_spmm_sweep(const uint32_t *slabs, const int32_t *wave_slab_ptr, const int32_t *wave_npieces, const int32_t *piece_slot,
-                   int64_t n_waves, int32_t row_cap, int32_t groups, const lgc_multi_row *multi, int32_t n_rows,
-                   const lgc_multi_row *multi_wide, int32_t n_wide, float *partials,
-                   int64_t table_rows, const float *x, int64_t x_stride, float *y, int64_t y_stride, const float *r,
-                   int64_t r_stride, float a, float b, int32_t dim, void *stream_) {
+// lgc_spmm_sweep, and with r2 (lgc_apply2) its combine with the second epilogue row: y = (b2 * r2 + b * r) + a * A x
+static int spmm_sweep(const uint32_t *slabs, const int32_t *wave_slab_ptr, const int32_t *wave_npieces, const int32_t *piece_slot,
+                      int64_t n_waves, int32_t row_cap, int32_t groups, const lgc_multi_row *multi, int32_t n_rows,
+                      const lgc_multi_row *multi_wide, int32_t n_wide, float *partials,
+                      int64_t table_rows, const float *x, int64_t x_stride, float *y, int64_t y_stride, const float *r,
+                      int64_t r_stride, const float *r2, int64_t r2_stride, float a, float b, float b2, int32_t dim,
+                      void *stream_) {
+    if (r2 && (!r || r2_stride < dim)) return LGC_E_INVAL;
+    if (r2 && !aligned_to(r2, 4)) return LGC_E_ALIGN;
     if (!slabs || !wave_slab_ptr || !wave_npieces || !piece_slot || !partials || !x || !y || n_waves < 0 ||
         n_waves % 4 != 0 || n_rows < 0 || n_wide < 0 || (n_rows > 0 && !multi) || (n_wide > 0 && !multi_wide) || row_cap < 1 ||
         row_cap > 254 || x == y)
@@ -3049,10 +3155,23 @@ int lgc_spmm_sweep(const uint32_t *slabs, const int32_t *wave_slab_ptr, const in
     sp.wt_store = wt_store_ok(table_rows, y_stride) ? 1 : 0;
     if (n_wide + n_rows > 0) {
         const int rows_per_block = (kBlock / kWave) * (kWave / cfg.lpr);
-        hipLaunchKernelGGL((k_sweep_combine<4>), dim3(n_wide + ceil_div(n_rows, rows_per_block)), dim3(kBlock), 0, stream, sp,
-                           multi_wide, n_wide, multi, n_rows, partials);
+        const dim3 grid(n_wide + ceil_div(n_rows, rows_per_block));
+        if (r2)
+            hipLaunchKernelGGL((k_sweep_combine2<4>), grid, dim3(kBlock), 0, stream, sp, multi_wide, n_wide, multi, n_rows, partials,
+                               EpilogueRow2{r2, r2_stride, b2});
+        else
+            hipLaunchKernelGGL((k_sweep_combine<4>), grid, dim3(kBlock), 0, stream, sp, multi_wide, n_wide, multi, n_rows, partials);
     }
     return (int)hipGetLastError();
+}
+
+int lgc_spmm_sweep(const uint32_t *slabs, const int32_t *wave_slab_ptr, const int32_t *wave_npieces, const int32_t *piece_slot,
+                   int64_t n_waves, int32_t row_cap, int32_t groups, const lgc_multi_row *multi, int32_t n_rows,
+                   const lgc_multi_row *multi_wide, int32_t n_wide, float *partials,
+                   int64_t table_rows, const float *x, int64_t x_stride, float *y, int64_t y_stride, const float *r,
+                   int64_t r_stride, float a, float b, int32_t dim, void *stream_) {
+    return spmm_sweep(slabs, wave_slab_ptr, wave_npieces, piece_slot, n_waves, row_cap, groups, multi, n_rows, multi_wide, n_wide,
+                      partials, table_rows, x, x_stride, y, y_stride, r, r_stride, nullptr, 0, a, b, 0.0f, dim, stream_);
 }
 
 int lgc_apply_route(const lgc_operator *op, int64_t table_rows, int64_t x_stride, int64_t y_stride, int64_t r_stride,
@@ -3155,6 +3274,26 @@ int lgc_apply(const lgc_operator *op, int64_t table_rows, const float *x, int64_
         }
     }
     return 0;
+}
+
+int lgc_apply2(const lgc_operator *op, int64_t table_rows, const float *x, int64_t x_stride, float *y, int64_t y_stride,
+               const float *r, int64_t r_stride, const float *r2, int64_t r2_stride, float a, float b, float b2, int32_t dim,
+               void *stream) {
+    const int route = lgc_apply_route(op, table_rows, x_stride, y_stride, r ? r_stride : 0, dim);
+    if (route < 0) return route;
+    if (!r || r_stride < dim || !r2 || r2_stride < dim) return LGC_E_INVAL;   // the second row comes with the first only
+    switch (route & ~LGC_ROUTE_WT_STORE) {
+    case LGC_ROUTE_SWEEP:
+    case LGC_ROUTE_SWEEP_WIDE:
+    case LGC_ROUTE_SWEEP_TWO_PASS: {
+        const lgc_sweep_arrays *sw = op->sweep;
+        return spmm_sweep(sw->slabs, sw->wave_slab_ptr, sw->wave_npieces, sw->piece_slot, sw->n_waves, sw->row_cap, sw->groups,
+                          sw->multi, sw->n_rows, sw->multi_wide, sw->n_wide, sw->partials, table_rows, x, x_stride, y, y_stride, r,
+                          r_stride, r2, r2_stride, a, b, b2, dim, stream);
+    }
+    default:
+        return LGC_E_DIM;     // no sweep for this operator and table (as lgc_spmm_sweep): tiles, chunks and rows keep one row
+    }
 }
 
 int lgc_hop_exchange(const lgc_operator *item_op, const lgc_operator *user_op, int64_t table_rows, const float *x,

@@ -649,10 +649,30 @@ class Operator:
         _native.check(min(code, 0), "lgc_apply_route")
         return _native.route_name(code)
 
-    def apply(self, x: Tensor, out: Tensor, a: float = 1.0, r: Optional[Tensor] = None, b: float = 0.0) -> Tensor:
-        """out[row] = a * (A x)[row] + b * r[row] for the rows of the plan: one ``lgc_apply`` on the current stream."""
+    def takes_second_row(self, x: Tensor, out: Tensor, r: Tensor) -> bool:
+        """Whether ``apply(x, out, r=r, r2=...)`` is served for these tables: only the band sweep's combine takes a second
+        epilogue row (``lgc_apply2``).  Launches nothing."""
+        return self.route(x, out, r).split("+")[0] in ("sweep", "sweep_wide", "sweep_two_pass")
+
+    def apply(self, x: Tensor, out: Tensor, a: float = 1.0, r: Optional[Tensor] = None, b: float = 0.0,
+              r2: Optional[Tensor] = None, b2: float = 0.0) -> Tensor:
+        """out[row] = a * (A x)[row] + b * r[row] for the rows of the plan: one ``lgc_apply`` on the current stream.
+        With ``r2`` (needs ``r``, and an operator that ``takes_second_row``):  (b2 * r2[row] + b * r[row]) + a * (A x)[row],
+        the bits of ``_native.lincomb(out, [(b2, r2), (b, r), (a, A x)])`` -- one ``lgc_apply2``."""
         import ctypes
         lib, c, dim, table_rows = self._apply_args(x, out, r)
+        if r2 is not None:
+            if r is None:
+                raise ValueError("r2 needs r")
+            _check_table(r2, "r2")
+            if r2.size(1) != dim:
+                raise ValueError("x, out, r and r2 must have the same width")
+            with torch.cuda.device(x.device):
+                code = lib.lgc_apply2(ctypes.byref(c), table_rows, _native.ptr(x), x.stride(0), _native.ptr(out), out.stride(0),
+                                      _native.ptr(r), r.stride(0), _native.ptr(r2), r2.stride(0), float(a), float(b), float(b2),
+                                      dim, _native.stream_of(x.device))
+            _native.check(code, "lgc_apply2")
+            return out
         with torch.cuda.device(x.device):
             code = lib.lgc_apply(ctypes.byref(c), table_rows, _native.ptr(x), x.stride(0), _native.ptr(out), out.stride(0),
                                  _native.ptr(r), 0 if r is None else r.stride(0), float(a), float(b), dim,
@@ -753,9 +773,17 @@ def apply_rows(op: "Operator", rows: Tensor, x: Tensor, out: Tensor, a: float = 
 # Measured on the cosmetics graph (profiles/EXPERIMENTS.md, "Middle-hop reduction"): T = 3 is the fastest at D=64 / K=3
 # (-2.0 %) and at D=90 / K=5 (-4.1 %); its G_L holds 0.82 entries per entry removed.  T = 4 (1.12) still gains at D=64 but
 # not at D=90, T >= 5 (1.37 and up) loses: the share limit 1.0 separates the T that pay from those that do not.
+# Those prices are the separate G_L launch's (LGCN_REDUCED_CONCAT=0).  With G_L inside the kept users' band sweep (the
+# default wherever "auto" runs at all, comment at REDUCED_CONCAT) an entry of G_L costs about a third less, and "auto" has
+# its own pair: T = ELIMINATE_AUTO_MAX_DEG_CONCAT = 4 and the share limit 1.25.  Measured with the concatenated operator
+# (profiles/EXPERIMENTS.md, "Layer sum in the item step; T = 4"): the plans of T = 3, 4, 5 all keep two rounds at D=64;
+# T = 4 against T = 3 is -18 .. -26 us of 1.49 ms at D=64 / K=3 and level at D=90 / K=5; T = 5 (share 1.37) is within the
+# noise of T = 4 at D=64, behind it at D=90, and 64 MB larger: the limit sits between 1.12 and 1.37.
 ELIMINATE_MAX_DEG = os.environ.get("LGCN_ELIMINATE_MAX_DEG", "auto")
 ELIMINATE_AUTO_MAX_DEG = int(os.environ.get("LGCN_ELIMINATE_AUTO_MAX_DEG", "3"))
 ELIMINATE_MAX_GRAM_SHARE = float(os.environ.get("LGCN_ELIMINATE_MAX_GRAM_SHARE", "1.0"))
+ELIMINATE_AUTO_MAX_DEG_CONCAT = int(os.environ.get("LGCN_ELIMINATE_AUTO_MAX_DEG_CONCAT", "4"))
+ELIMINATE_MAX_GRAM_SHARE_CONCAT = float(os.environ.get("LGCN_ELIMINATE_MAX_GRAM_SHARE_CONCAT", "1.25"))
 # G_L's rows are long (mean 89 entries at T = 4 on the cosmetics graph, the longest 23.6 k) and gather from the small item
 # table: their own chunk length
 GRAM_CHUNK_LEN = int(os.environ.get("LGCN_GRAM_CHUNK_LEN", "256"))
@@ -1049,7 +1077,12 @@ class PropGraph:
             return None
         forced = self.eliminate_max_deg
         auto = forced is None and ELIMINATE_MAX_DEG == "auto"
-        max_deg = int(forced) if forced is not None else (ELIMINATE_AUTO_MAX_DEG if auto else int(ELIMINATE_MAX_DEG))
+        # "auto" runs only where the item half takes the band sweep; the reduced layers then carry G_L inside the kept users'
+        # sweep unless LGCN_REDUCED_CONCAT is 0, and that case has its own T and share limit (comment at ELIMINATE_MAX_DEG)
+        concat = REDUCED_CONCAT != "0"
+        auto_deg, auto_share = ((ELIMINATE_AUTO_MAX_DEG_CONCAT, ELIMINATE_MAX_GRAM_SHARE_CONCAT) if concat else
+                                (ELIMINATE_AUTO_MAX_DEG, ELIMINATE_MAX_GRAM_SHARE))
+        max_deg = int(forced) if forced is not None else (auto_deg if auto else int(ELIMINATE_MAX_DEG))
         if max_deg <= 0:
             return None
         key = ("reduced", max_deg, auto)
@@ -1060,7 +1093,7 @@ class PropGraph:
             got = self._build_reduced(max_deg)
             if got is not None and auto:
                 removed = self.forward_op.nnz - got.csr.nnz
-                if got.csr.gram_nnz > ELIMINATE_MAX_GRAM_SHARE * removed:
+                if got.csr.gram_nnz > auto_share * removed:
                     got = None
         self._halves[key] = got
         return got

@@ -104,6 +104,12 @@ def bipartite_sum(user_op: Operator, item_op: Operator, split: int, x0: Tensor, 
     and the weighted sums over layers are taken on the small item tables only (``lgc_lincomb``, in the
     reference's own order: out = out + x * alpha).  Same K item steps + K user steps as K plain hops.
 
+    With equal alphas, K = 2 or 3 and a band-sweep item step, that sum has no launch of its own either: the item step of
+    layer K - 1 writes  mix = (alpha_{K-2} x_{K-3} + alpha_{K-1} x_{K-2}) + alpha_K x_{K-1}  over the item rows into the
+    block where x_{K-1}[items] would go -- nothing else reads that block -- with the prior terms as epilogue rows
+    (``Operator.apply(..., r2=, b2=)``, lgc_apply2), in lgc_lincomb's association: the same bits, one launch, one write
+    and one read of the block less (``mix_in_item_step`` below; LGCN_MIX_IN_ITEM_STEP=0 keeps the lgc_lincomb).
+
     ``final_rows`` (int64 node ids on the device, users and items alike): the caller will only ever read these rows of the
     result -- a training step scores 2B label pairs (src/lightgcn.py:123-125).  The LAST user step, whose 1.6 M output rows
     nothing else consumes, is then computed for the listed user rows only (``lgc_spmm_rows``: a few thousand gathers, the
@@ -177,11 +183,40 @@ def bipartite_sum(user_op: Operator, item_op: Operator, split: int, x0: Tensor, 
     # (only when a result row is whole cache lines: the combine's stores into 360-byte rows cost more than the lincomb saves,
     # 4.67 vs 4.65 ms per K=5, D=90 step; 1.607 vs 1.623 ms at K=3, D=64)
     uniform = UNIFORM_ALPHA_SHORTCUT and all(a == alphas[0] for a in alphas) and (UNIFORM_ALPHA_SHORTCUT == "force" or x0.size(1) % 32 == 0)
+
+    def mix_in_item_step(out_t: Tensor) -> bool:
+        """Layer K-1's item step writes mix = sum_{l=1..K} alpha_l x_{l-1}[items] where x_{K-1}[items] would go
+        (LGCN_MIX_IN_ITEM_STEP): that block has no other reader -- the user step of layer K-1 gathers table K-2, layer K's
+        item step gathers table K-1 below ``split`` only (user rows and gaps) and x_{K-2}[items] from the gaps or from
+        table K-2 (gram_op) -- so the lgc_lincomb of the last layer, its write and its read of the block go away.  The
+        prior terms ride as epilogue rows in lgc_lincomb's association, ((a_1 x_0 + a_2 x_1) + a_3 x_2): the same bits.
+        One or two prior terms (K = 2, 3) and a band-sweep item step only; False = nothing launched, today's path."""
+        if not (MIX_IN_ITEM_STEP and uniform and final_rows is None and k in (2, 3)):
+            return False
+        if red is None or k == 2:
+            op, o = item_op, 0                                                  # layer 1 is always the full operator
+        elif cc is not None:
+            op, o = cc.item_op, cc.offset
+        else:
+            return False                                                        # G_L as a separate launch: unchanged
+        x = tables[k - 2][o:]                               # x_{K-2}: its user rows are gathered, its item rows are r
+        if not op.takes_second_row(x, out_t[o:], x):
+            return False
+        assert op.sweep_cols is not None and o + op.sweep_cols[1] <= split      # the item steps gather no item row
+        if k == 2:
+            op.apply(x, out_t[o:], a=alphas[2], r=x, b=alphas[1])
+        else:
+            op.apply(x, out_t[o:], a=alphas[3], r=x, b=alphas[2], r2=tables[0][o:], b2=alphas[1])
+        return True
+
+    mixed = False
     for layer in range(1, k + 1):
         with _HopSpan():
-            nxt = scratch_table(x0)
+            nxt = None if mixed else scratch_table(x0)
             if layer < k:
-                if red is None or layer == 1:
+                if layer == k - 1 and mix_in_item_step(nxt):
+                    mixed = True                                                # nxt[items] = mix, not x_l[items]
+                elif red is None or layer == 1:
                     item_op.apply(tables[-1], nxt)                              # x_l[items]
                 else:
                     item_step(layer, nxt)
@@ -203,8 +238,11 @@ def bipartite_sum(user_op: Operator, item_op: Operator, split: int, x0: Tensor, 
                         _native.lincomb(rest[split:], [(alphas[l], tables[l][split:]) for l in range(0, k)])
                     apply_rows(item_op, final_rows, tables[-1], out, a=alphas[k], r=rest, b=1.0, split=True)
                 elif uniform:
-                    mix = nxt                                                   # item rows: sum_l alpha_l x_{l-1}
-                    _native.lincomb(mix[split:], [(alphas[l], tables[l - 1][split:]) for l in range(1, k + 1)])
+                    if mixed:
+                        mix = tables[-1]                                        # written by layer K-1's item step
+                    else:
+                        mix = nxt                                               # item rows: sum_l alpha_l x_{l-1}
+                        _native.lincomb(mix[split:], [(alphas[l], tables[l - 1][split:]) for l in range(1, k + 1)])
                     if red is None:
                         item_op.apply(tables[-1], out, a=alphas[k], r=mix, b=1.0)   # out[items] = mix + alpha_K x_K[items]
                     else:
@@ -233,8 +271,11 @@ def _layer_sum(graph: PropGraph, x: Tensor, alphas: tuple, transpose: bool, fina
     return horner_hops(graph.transpose_op if transpose else graph.forward_op, x, alphas)
 
 
+# ... and the item step before it writes the layer sum the last user step gathers (bipartite_sum.mix_in_item_step,
+# lgc_apply2); "0": that sum as a lgc_lincomb of its own in the last layer
+MIX_IN_ITEM_STEP = os.environ.get("LGCN_MIX_IN_ITEM_STEP", "1") == "1"
 # equal alphas: the last item step writes the result's item block itself (bipartite_sum); "0" keeps the two lincombs
-UNIFORM_ALPHA_SHORTCUT = {"0": False, "force": "force"}.get(os.environ.get("LGCN_UNIFORM_ALPHA_SHORTCUT", "1"), True)
+UNIFORM_ALPHA_SHORTCUT ={"0": False, "force": "force"}.get(os.environ.get("LGCN_UNIFORM_ALPHA_SHORTCUT", "1"), True)
 # the forward of a scoring step computes the last user step only for the rows its label pairs name (bipartite_sum)
 SCORED_ROWS_ONLY = os.environ.get("LGCN_SCORED_ROWS_ONLY", "1") == "1"
 # ... and the last ITEM step as well (lgc_spmm_rows_split); "0": the full item step, as get_embedding runs it

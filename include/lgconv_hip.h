@@ -420,6 +420,21 @@ int lgc_apply_route(const lgc_operator *op, int64_t table_rows, int64_t x_stride
 int lgc_apply(const lgc_operator *op, int64_t table_rows, const float *x, int64_t x_stride, float *y, int64_t y_stride,
               const float *r, int64_t r_stride, float a, float b, int32_t dim, void *stream);
 
+/*
+ * lgc_apply with a SECOND epilogue row, on the three sweep routes only:
+ *     y[row] = (b2 * r2[row] + b * r[row]) + a * (A x)[row]
+ * every product rounded before its add, in this association -- the bits of lgc_apply(x, t) followed by
+ * lgc_lincomb(y, {(b2, r2), (b, r), (a, t)}), without the table t and the second launch: the item step before the last
+ * layer writes the layer sum the last user step gathers (bipartite_sum).  The sweep runs as in lgc_apply; the combine is a
+ * kernel of its own (k_sweep_combine2).  r and r2 are both required (LGC_E_INVAL for either missing or a stride below dim,
+ * LGC_E_ALIGN for one that is not dword aligned); r may alias y as in lgc_apply (a lane reads the elements it then writes),
+ * r2 may too.  The route is asked of lgc_apply_route first: its errors come back unchanged, and an operator that would not take
+ * LGC_ROUTE_SWEEP / _SWEEP_WIDE / _SWEEP_TWO_PASS at this geometry is refused with LGC_E_DIM before anything is launched.
+ */
+int lgc_apply2(const lgc_operator *op, int64_t table_rows, const float *x, int64_t x_stride, float *y, int64_t y_stride,
+               const float *r, int64_t r_stride, const float *r2, int64_t r2_stride, float a, float b, float b2, int32_t dim,
+               void *stream);
+
 typedef int (*lgc_exchange_fn)(float *block, int64_t rows, int64_t row_stride, int32_t dim, void *stream, void *user);
 
 int lgc_hop_exchange(const lgc_operator *item_op, const lgc_operator *user_op, int64_t table_rows, const float *x,
