@@ -119,11 +119,10 @@ def dense_fp64(op, n):
     return a
 
 
-def layer_sum_fp64(op, x0, alphas):
-    """sum_l alpha_l A^l x0 in fp64 on the host, A from the operator's own fp32 values (sparse product)."""
+def layer_sum_coo_fp64(rows, cols, vals, x0, alphas):
+    """sum_l alpha_l A^l x0 in fp64 on the host for A[rows[e], cols[e]] += vals[e] (sparse product; no device)."""
     n = x0.size(0)
-    _, cols, vals, rows = csr_host(op)
-    a = torch.sparse_coo_tensor(torch.stack([rows, cols]), vals, (n, n)).coalesce()
+    a = torch.sparse_coo_tensor(torch.stack([rows, cols]), vals.double(), (n, n)).coalesce()
     x = x0.cpu().double()
     out = alphas[0] * x
     for alpha in alphas[1:]:
@@ -132,10 +131,17 @@ def layer_sum_fp64(op, x0, alphas):
     return out
 
 
+def layer_sum_fp64(op, x0, alphas):
+    """sum_l alpha_l A^l x0 in fp64 on the host, A from the operator's own fp32 values (sparse product)."""
+    _, cols, vals, rows = csr_host(op)
+    return layer_sum_coo_fp64(rows, cols, vals, x0, alphas)
+
+
 def alphas_for(k, equal):
+    """K + 1 weights, K <= 7: the reference's 1 / (K + 1), or a falling sequence of all different values."""
     if equal:
         return tuple([1.0 / (k + 1)] * (k + 1))
-    return tuple(float(v) for v in (0.5 ** np.arange(k + 1) * np.array([1.0, 0.9, 1.1, 0.7, 1.3, 0.8][:k + 1])))
+    return tuple(float(v) for v in (0.5 ** np.arange(k + 1) * np.array([1.0, 0.9, 1.1, 0.7, 1.3, 0.8, 1.2, 0.6][:k + 1])))
 
 
 def eliminated_users(op, split, max_deg):
