@@ -202,6 +202,9 @@ SIGNATURES = {
                                c_int32, c_int32, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "lgc_list_diversity": (c_int, [c_void_p, c_int64, c_int64, c_int32, c_void_p, c_void_p, c_int64, c_int64, c_int32,
                                    POINTER(c_int32), c_int32, c_void_p, c_int64, c_void_p, c_void_p]),
+    "lgc_sample_hard_triples": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_uint64,
+                                        c_uint64, c_int32, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_void_p, c_void_p,
+                                        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 
@@ -271,6 +274,7 @@ ATTR_MAX_TARGETS = 64  # LGC_ATTR_MAX_TARGETS: target columns of one lgc_attribu
 ATTR_MAX_TOP = 8       # LGC_ATTR_MAX_TOP
 NEIGHBORS_MAX_K = 64   # LGC_NEIGHBORS_MAX_K
 RERANK_MAX_CAND = 256  # LGC_RERANK_MAX_CAND
+HARDNEG_MAX_CAND = 256 # LGC_HARDNEG_MAX_CAND
 RERANK_ROUTES = {1: "lds", 2: "global"}   # lgc_rerank_route's codes (LGC_RERANK_ROUTE_*)
 
 

@@ -105,8 +105,8 @@ class TripleSampler:
                *pairs_to_csr(n_users, ign_user, ign_item, sort_unique=True))
         return cls(n_users, n_items, {}, {}, device, seed, _csr=csr)
 
-    def sample(self, batch_size: int) -> Tuple[Tensor, Tensor, Tensor]:
-        """(users, pos_items, neg_items), each int64 [batch_size] on the device."""
+    def _draw_users(self, batch_size: int) -> Tuple[Tensor, Tensor, Tensor]:
+        """The users of a batch (random.sample without replacement among the users with positives) and the two outputs."""
         n_cand = self.candidates.numel()
         if batch_size > n_cand:
             raise ValueError("Sample larger than population or is negative")       # random.sample's message
@@ -114,6 +114,11 @@ class TripleSampler:
         users = self.candidates[pick].contiguous()
         pos = torch.empty(batch_size, dtype=torch.int64, device=self.device)
         neg = torch.empty(batch_size, dtype=torch.int64, device=self.device)
+        return users, pos, neg
+
+    def sample(self, batch_size: int) -> Tuple[Tensor, Tensor, Tensor]:
+        """(users, pos_items, neg_items), each int64 [batch_size] on the device."""
+        users, pos, neg = self._draw_users(batch_size)
         lib = _native.load()
         with torch.cuda.device(self.device):
             code = lib.lgc_sample_triples(
@@ -124,6 +129,63 @@ class TripleSampler:
         _native.check(code, "lgc_sample_triples")
         self.step += 1
         return users, pos, neg
+
+    def sample_hard(self, batch_size: int, table: Tensor, candidates: int = 8, with_info: bool = False):
+        """``sample()`` with hard negatives (dynamic negative sampling): each triple draws up to ``candidates`` admissible
+        negatives, scores them against the user's row of ``table`` and keeps the highest-scored one -- one HIP launch
+        (``lgc_sample_hard_triples``; contract in include/lgconv_hip.h).
+
+        The users are drawn as ``sample()`` draws them, from the same generator, and the same ``step`` counter advances, so
+        ``candidates=1`` returns the triples ``sample()`` would have returned at that point, and so does a table of zeros.
+
+        ``table``: fp32 ``[n_users + n_items, dim]`` on the sampler's device, unit inner stride, any row stride >= dim; its
+        user and item halves are passed as views.  Two tables make sense:
+
+        * ``model.embedding.weight.detach()`` -- free and always current, but layer 0 only;
+        * ``model.get_embedding(edge_index, edge_weight)`` under ``torch.no_grad()`` -- what the model scores with, at the
+          price of one forward; refresh it every R steps.
+
+        Returns ``(users, pos, neg)``; with ``with_info`` also ``(neg_score fp32, neg_attempt int32, n_admissible int32)``,
+        each ``[batch_size]``: the winner's score, its 1-based attempt number, and how many candidates were scored.
+
+        Single device only: a rank's table of the partitioned trainer holds stale rows of the nodes other ranks own.  Not
+        for use inside a captured graph either: ``step`` is passed by value."""
+        if not isinstance(table, Tensor):
+            raise TypeError("table must be a torch.Tensor")
+        if isinstance(candidates, bool) or not isinstance(candidates, int):
+            raise TypeError("candidates must be an int")
+        if not 1 <= candidates <= _native.HARDNEG_MAX_CAND:
+            raise ValueError(f"candidates must be in 1..{_native.HARDNEG_MAX_CAND}, got {candidates}")
+        if table.dtype != torch.float32:
+            raise TypeError(f"table must be float32, got {table.dtype}")
+        if table.dim() != 2 or table.size(1) < 1:
+            raise ValueError(f"table must be [n_users + n_items, dim], got {tuple(table.shape)}")
+        if table.size(0) != self.n_users + self.n_items:
+            raise ValueError(f"table has {table.size(0)} rows, the sampler's graph {self.n_users + self.n_items}")
+        if table.size(0) > 1 and (table.stride(1) != 1 or table.stride(0) < table.size(1)):
+            raise ValueError("table needs unit inner stride and a row stride >= dim")
+        if table.device.type != self.device.type or (self.device.index is not None and table.device.index != self.device.index):
+            raise ValueError(f"table is on {table.device}, the sampler on {self.device}")
+        table = table.detach()
+        users, pos, neg = self._draw_users(batch_size)
+        info = None
+        if with_info:
+            info = (torch.empty(batch_size, dtype=torch.float32, device=self.device),
+                    torch.empty(batch_size, dtype=torch.int32, device=self.device),
+                    torch.empty(batch_size, dtype=torch.int32, device=self.device))
+        stride = table.stride(0) if table.size(0) > 1 else table.size(1)
+        user_half, item_half = table[:self.n_users], table[self.n_users:]
+        lib = _native.load()
+        with torch.cuda.device(self.device):
+            code = lib.lgc_sample_hard_triples(
+                _native.ptr(users), batch_size, _native.ptr(self.pos_ptr), _native.ptr(self.pos_items),
+                _native.ptr(self.ign_ptr), _native.ptr(self.ign_items), self.n_users, self.n_items,
+                self.seed, self.step, candidates, user_half.data_ptr(), stride, item_half.data_ptr(), stride,
+                table.size(1), _native.ptr(pos), _native.ptr(neg), *(_native.ptr(t) for t in (info or (None,) * 3)),
+                _native.ptr(self.status), _native.stream_of(self.device))
+        _native.check(code, "lgc_sample_hard_triples")
+        self.step += 1
+        return (users, pos, neg, *info) if with_info else (users, pos, neg)
 
     def check(self) -> None:
         """Synchronising check of the kernel's status word."""

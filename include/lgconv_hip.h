@@ -1051,6 +1051,54 @@ int lgc_list_diversity(const float *items, int64_t item_stride, int64_t n_items,
                        const int64_t *lists, int64_t list_stride, int64_t n_rows, int32_t k, const int32_t *cutoffs,
                        int32_t n_cutoffs, double *out, int64_t out_stride, int32_t *status, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Hard negatives (an addition to ABI 14: exports only): dynamic negative sampling for BPR.  A uniformly drawn negative
+ * soon scores far below the positive and its gradient weight sigmoid(neg - pos) is almost nothing; here every sample
+ * draws up to n_cand admissible candidates, scores them against the user's row of the given table and trains against the
+ * highest-scored one.  One launch, one wavefront per sample; upstream's batch_loader (src/utils_v2.py:168-181) has no
+ * counterpart.
+ *
+ *   users .. step   as lgc_sample_triples, and its stream exactly: sample i has
+ *              key = mix64(mix64(seed) ^ mix64(step * STEP_MUL + i)), the positive is
+ *              pos_items[pos_ptr[u] + bounded(mix64(key), count)], and attempt a = 1 .. 256 proposes the node
+ *              n_users + bounded(mix64(key + ATTEMPT_MUL * a), n_items); an attempt is admissible when its node is not in
+ *              the user's sorted ignore set (ign_items may be NULL where every set is empty)
+ *   n_cand     1 .. LGC_HARDNEG_MAX_CAND.  The candidates of sample i are the first n_cand admissible attempts among
+ *              attempts 1 .. 256, in attempt order: fewer where the 256 attempts hold fewer; a node drawn twice is two
+ *              candidates and is scored twice
+ *   user_table, user_stride   fp32 [n_users, dim], rows user_stride >= dim floats apart
+ *   item_table, item_stride   fp32 [n_items, dim], rows item_stride >= dim apart: row c - n_users is node c's.  Columns at
+ *              or past dim are never read: a row may end there
+ *   pos_out, neg_out   int64 [n]: the positive, and the winner's node id
+ *   neg_score  fp32 [n] or NULL: the winner's score;  neg_attempt int32 [n] or NULL: its attempt number, 1-based;
+ *   n_admissible   int32 [n] or NULL: how many candidates were taken, 0 .. n_cand
+ *   status     LGC_ST_INDEX_OOB, LGC_ST_SAMPLER_EXHAUSTED as lgc_sample_triples
+ * Score, bit for bit.  The score of candidate c is dot(user_table[u], item_table[c - n_users]) with the bits lgc_score_rows
+ * writes for those two rows: one chain of fp32 fused multiply-adds over d = 0 .. round_up(dim, 4) - 1, ascending from +0,
+ * with zeros past dim.  neg_score is the chain's value (a -0 stays -0; any NaN stands for any NaN).
+ * Winner.  The first element in lgc_mask_topk's total order over the candidates' scores -- every NaN first, then +inf, the
+ * finite values descending with -0 = +0, then -inf -- equal scores going to the earlier attempt.  The order is strict: the
+ * result depends on the arguments alone, not on how attempts are spread over lanes or rounds, nor on the run.  No float
+ * atomics.  It follows that n_cand = 1 returns the pos_out and neg_out of lgc_sample_triples for the same arguments, and
+ * that a table of zeros does so at any n_cand.
+ * No admissible attempt among the 256: LGC_ST_SAMPLER_EXHAUSTED is set, neg_out[i] is the last draw as in
+ * lgc_sample_triples, neg_attempt[i] = 256, n_admissible[i] = 0 and neg_score[i] is that draw's score.
+ * A user outside [0, n_users) or without positives: LGC_ST_INDEX_OOB is set, pos_out[i] = neg_out[i] = n_users,
+ * neg_score[i] = 0, neg_attempt[i] = 0, n_admissible[i] = 0; no table address is formed from the id.
+ * Errors, before any launch: LGC_E_DIM (as lgc_dim_ok); LGC_E_INVAL (a null required pointer, a negative n, n_users < 0,
+ * n_items < 1, a stride below dim); LGC_E_RANGE (n_cand outside 1 .. LGC_HARDNEG_MAX_CAND, or n or n_users + n_items
+ * >= 2^31).  n == 0 validates, launches nothing and returns 0.
+ * ------------------------------------------------------------------------------------- */
+#define LGC_HARDNEG_MAX_CAND 256         /* = the sampler's attempts: every attempt can be a candidate */
+int lgc_sample_hard_triples(const int64_t *users, int64_t n,
+                            const int32_t *pos_ptr, const int64_t *pos_items,
+                            const int32_t *ign_ptr, const int64_t *ign_items,
+                            int64_t n_users, int64_t n_items, uint64_t seed, uint64_t step, int32_t n_cand,
+                            const float *user_table, int64_t user_stride,
+                            const float *item_table, int64_t item_stride, int32_t dim,
+                            int64_t *pos_out, int64_t *neg_out, float *neg_score, int32_t *neg_attempt,
+                            int32_t *n_admissible, int32_t *status, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

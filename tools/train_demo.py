@@ -5,6 +5,12 @@ backward -> Adam), then recommendK + MARK_MAPK on held-out purchases.  Data are 
 (users and items drawn around a few taste centres) so that there is something to learn.
 
     python tools/train_demo.py [--users 20000 --items 2000 --epochs 3 --dim 64 --layers 3]
+    python tools/train_demo.py --hard-negatives 8 [--refresh 10]
+
+--hard-negatives M trains every triple against the hardest of M sampled negatives (TripleSampler.sample_hard; 0 = one
+uniform negative, the reference's batch_loader).  --refresh R scores them with the propagated table, recomputed every R
+steps; 0 scores them with the layer-0 table, which costs nothing.  The epoch line carries the mean attempt number of the
+negative (null without --hard-negatives: the uniform sampler does not report it) and the mean BPR gradient weight sigmoid(neg - pos): how much of a step is spent on gradients that matter.
 """
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -28,13 +34,14 @@ def latent_interactions(n_users, n_items, per_user, seed):
     return np.concatenate(users), np.concatenate(items)
 
 
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--users", type=int, default=20000); ap.add_argument("--items", type=int, default=2000)
     ap.add_argument("--per-user", type=int, default=12); ap.add_argument("--epochs", type=int, default=3)
     ap.add_argument("--dim", type=int, default=64); ap.add_argument("--layers", type=int, default=3)
     ap.add_argument("--batch", type=int, default=1024); ap.add_argument("--k", type=int, default=20)
-    args = ap.parse_args()
+    ap.add_argument("--hard-negatives", type=int, default=0, metavar="M"); ap.add_argument("--refresh", type=int, default=0, metavar="R")
+    args = ap.parse_args(argv)
     dev = torch.device("cuda:0")
     u, i = latent_interactions(args.users, args.items, args.per_user, 0)
     rng = np.random.default_rng(1)
@@ -60,12 +67,21 @@ def main():
     model = lg.LightGCN(n_users + n_items, args.dim, args.layers).to(dev)
     opt = torch.optim.Adam(model.parameters(), 0.005)
     n_batch = max(1, len(train) // (args.batch * 40))                   # train_lightgcn.py:92: train_size // (B * 40)
-    log = []
+    log, table, step = [], None, 0
     for epoch in range(args.epochs):
-        model.train(); t0 = time.perf_counter(); losses = []
+        model.train(); t0 = time.perf_counter(); losses, attempts, weights = [], [], []
         for _ in range(n_batch):                                        # train_lightgcn.py:129-151
             opt.zero_grad()
-            users, pos, neg = sampler.sample(args.batch)
+            if args.hard_negatives > 0:
+                if args.refresh > 0 and step % args.refresh == 0:
+                    with torch.no_grad():
+                        table = model.get_embedding(edge_index, edge_weight)
+                users, pos, neg, _, attempt, _ = sampler.sample_hard(
+                    args.batch, table if args.refresh > 0 else model.embedding.weight.detach(), args.hard_negatives, with_info=True)
+                attempts.append(attempt.float().mean())
+            else:
+                users, pos, neg = sampler.sample(args.batch)
+            step += 1
             labels = torch.stack((torch.cat([users, users]), torch.cat([pos, neg])))
             out = model(edge_index, labels, edge_weight)
             size = len(users)
@@ -75,13 +91,16 @@ def main():
             (bpr + reg).backward()
             opt.step()
             losses.append(bpr.item())
+            weights.append(torch.sigmoid(out.detach()[size:] - out.detach()[:size]).mean().item())
         torch.cuda.synchronize(); dt = time.perf_counter() - t0
         model.eval()
         with torch.no_grad():                                           # train_lightgcn.py:155-162
             top = model.recommendK(edge_index, edge_weight, n_users, n_items, seen, list(test_pos["user_id_idx"]), args.k)
             precision, recall, _ = model.MARK_MAPK(test_pos, top, args.k)
         log.append({"epoch": epoch, "bpr": float(np.mean(losses)), f"P@{args.k}": float(precision),
-                    f"R@{args.k}": float(recall), "batches": n_batch, "s": round(dt, 2)})
+                    f"R@{args.k}": float(recall), "batches": n_batch, "s": round(dt, 2),
+                    "neg_attempt": float(torch.stack(attempts).mean().item()) if attempts else None,
+                    "grad_weight": float(np.mean(weights))})
         print(json.dumps(log[-1]), flush=True)
     sampler.check(); lg.check_index_status()
     return log
