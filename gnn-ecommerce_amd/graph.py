@@ -743,6 +743,11 @@ def apply_rows(op: "Operator", rows: Tensor, x: Tensor, out: Tensor, a: float = 
     lib = _native.load()
     p = op.plan
     n_ids = rows.numel()
+    # An operator without a single entry (a rank of a partition that owns no user: its local edge list is empty) has no
+    # allocation behind ``entries``, and the C ABI refuses a NULL entry array while ids are listed.  Every row of such an
+    # operator is empty, so no entry is ever read: the row pointer's address stands in, and the listed rows come out as
+    # a * 0 + b * r like any other row without entries.
+    entries = _native.ptr(op.entries) if op.entries.size(0) else _native.ptr(op.rowptr)
     with torch.cuda.device(x.device):
         if split:
             if n_ids == 0:
@@ -750,14 +755,14 @@ def apply_rows(op: "Operator", rows: Tensor, x: Tensor, out: Tensor, a: float = 
             if out.size(0) < (n_ids if compact else p.row_end):
                 raise ValueError("out has too few rows")
             work, partials = _rows_split_scratch(x.device, n_ids, dim)
-            code = lib.lgc_spmm_rows_split(_native.ptr(op.rowptr), _native.ptr(op.entries), p.row_begin, p.row_end, _native.ptr(rows),
+            code = lib.lgc_spmm_rows_split(_native.ptr(op.rowptr), entries, p.row_begin, p.row_end, _native.ptr(rows),
                                            n_ids, x.size(0), _native.ptr(x), x.stride(0), _native.ptr(out), out.stride(0),
                                            out.size(0), _native.ptr(r), 0 if r is None else r.stride(0), float(a), float(b), dim,
                                            int(compact), _native.ptr(work), _native.ptr(partials), partials.size(0),
                                            _native.stream_of(x.device))
             _native.check(code, "lgc_spmm_rows_split")
             return out
-        code = lib.lgc_spmm_rows(_native.ptr(op.rowptr), _native.ptr(op.entries), p.row_begin, p.row_end, _native.ptr(rows),
+        code = lib.lgc_spmm_rows(_native.ptr(op.rowptr), entries, p.row_begin, p.row_end, _native.ptr(rows),
                                  n_ids, min(x.size(0), out.size(0)), _native.ptr(x), x.stride(0), _native.ptr(out),
                                  out.stride(0), _native.ptr(r), 0 if r is None else r.stride(0), float(a), float(b), dim,
                                  _native.stream_of(x.device))

@@ -97,7 +97,9 @@ class PartitionedTrainer:
         self._hyper_done = [None] * self._ring
         if dev.type == "cuda":
             self._hyper_host = self._hyper_host.pin_memory()
-        if pp.u1 <= pp.u0:
+        # decided on the ranges every rank holds, not on this rank's own: the ranks refuse together, instead of one rank
+        # raising while its peers construct and then wait for it in the first all-reduce
+        if any(hi <= lo for lo, hi in pp.ranges):
             raise ValueError("this rank owns no user rows: a partition with more ranks than users cannot train")
         self.stats = torch.zeros(3, dtype=torch.float32, device=dev)
         self.use_graphs = bool(graphs) and dev.type == "cuda"

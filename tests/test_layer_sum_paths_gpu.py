@@ -37,6 +37,7 @@ import torch
 import layer_sum_support as S
 from conftest import rel_fro
 from eliminate_support import alphas_for
+from partition_edges_support import loss_fp64
 import gnn_ecommerce_amd as lg
 from gnn_ecommerce_amd import _native, propagate, synth
 from gnn_ecommerce_amd import graph as G
@@ -326,20 +327,6 @@ def triples():
     pos[:4] = torch.tensor([S.HUB, S.HUB, S.LIGHT[0], S.SINGLE]) + S.N_USERS
     neg[:2] = torch.tensor([S.EMPTY, S.SINGLE]) + S.N_USERS
     return users, pos, neg
-
-
-def loss_fp64(w, coo, alphas, users, pos, neg, decay):
-    """(scores, loss) of one training step in fp64 on the host: the layer sum, the pair dots, then the model's own loss
-    expressions (``BPRLoss``, ``regularization_loss``) on plain torch ops."""
-    rows, cols, vals = coo
-    x = w
-    out = alphas[0] * x
-    for alpha in alphas[1:]:
-        x = torch.zeros_like(x).index_add(0, rows, vals.view(-1, 1) * x[cols])
-        out = out + alpha * x
-    b = users.numel()
-    scores = (out[torch.cat([users, users])] * out[torch.cat([pos, neg])]).sum(-1)
-    return scores, lg.BPRLoss(0)(scores[:b], scores[b:]) * b + lg.regularization_loss(w, b, users, pos, neg, decay)
 
 
 @pytest.mark.parametrize("seeded", (False, True), ids=("dense_backward", "seeded_backward"))

@@ -23,7 +23,7 @@ def _free_port():
     return path
 
 
-def _worker(rank, world, port, layers, dim, alpha_kind, q):
+def _worker(rank, world, port, layers, dim, alpha_kind, q, graph=None):
     sys.path.insert(0, ROOT)
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     torch.set_num_threads(2)
@@ -33,8 +33,14 @@ def _worker(rank, world, port, layers, dim, alpha_kind, q):
         from oracle import lightgcn_oracle as oracle
         from gnn_ecommerce_amd import synth
         from gnn_ecommerce_amd.partition import PartitionedPropagator
-        g = synth.make_bipartite(600, 90, 5000, seed=7)
-        ei, ew = g.coo()
+        if graph is None:
+            g = synth.make_bipartite(600, 90, 5000, seed=7)
+            ei, ew = g.coo()
+        else:                                           # a named graph of tests/partition_edges_support.py
+            import types
+            import partition_edges_support
+            ei, ew, n_users, n_items = partition_edges_support.graph(graph)
+            g = types.SimpleNamespace(n_users=n_users, n_items=n_items, num_nodes=n_users + n_items)
         n = g.num_nodes
         x0 = synth.xavier_table(n, dim, 1)
         alpha = oracle.default_alpha(layers) if alpha_kind == "uniform" else torch.linspace(0.5, 0.1, layers + 1)
@@ -60,12 +66,17 @@ def _worker(rank, world, port, layers, dim, alpha_kind, q):
         dist.destroy_process_group()
 
 
-@pytest.mark.parametrize("world,layers,dim,alpha_kind", [(2, 3, 64, "uniform"), (3, 2, 90, "ramp"), (2, 1, 16, "ramp"), (8, 3, 64, "uniform")])
-def test_partitioned_propagate_matches_single_process_oracle(world, layers, dim, alpha_kind):
+# the last case: ``hub_last`` of tests/partition_edges_support.py at world 3 -- rank 0 owns every user, two ranges are empty:
+# ``gather_users``' padded all-gather with hi == lo on two owners
+@pytest.mark.parametrize("world,layers,dim,alpha_kind,graph", [
+    pytest.param(2, 3, 64, "uniform", None, id="2-3-64-uniform"), pytest.param(3, 2, 90, "ramp", None, id="3-2-90-ramp"),
+    pytest.param(2, 1, 16, "ramp", None, id="2-1-16-ramp"), pytest.param(8, 3, 64, "uniform", None, id="8-3-64-uniform"),
+    pytest.param(3, 3, 7, "ramp", "hub_last", id="3-3-7-ramp-hub_last")])
+def test_partitioned_propagate_matches_single_process_oracle(world, layers, dim, alpha_kind, graph):
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     port = _free_port()
-    procs = [ctx.Process(target=_worker, args=(r, world, port, layers, dim, alpha_kind, q)) for r in range(world)]
+    procs = [ctx.Process(target=_worker, args=(r, world, port, layers, dim, alpha_kind, q, graph)) for r in range(world)]
     for p in procs:
         p.start()
     results = dict(q.get(timeout=180) for _ in range(world))
@@ -73,8 +84,14 @@ def test_partitioned_propagate_matches_single_process_oracle(world, layers, dim,
         p.join(timeout=60)
         assert p.exitcode == 0
     ranges = results[0]["ranges"]
-    assert ranges[0][0] == 0 and ranges[-1][1] == 600
-    assert sum(r["local_nnz"] for r in results.values()) == 2 * 5000          # shards partition the edges
+    n_users, nnz = 600, 2 * 5000
+    if graph is not None:
+        import partition_edges_support
+        ei, _, n_users, _ = partition_edges_support.graph(graph)
+        nnz = ei.size(1)
+        assert ranges == [(0, n_users), (n_users, n_users), (n_users, n_users)]
+    assert ranges[0][0] == 0 and ranges[-1][1] == n_users
+    assert sum(r["local_nnz"] for r in results.values()) == nnz               # shards partition the edges
     for rank, r in results.items():
         assert r["ranges"] == ranges
         assert r["own_users"] <= 1e-5 and r["items"] <= 1e-5 and r["gathered"] <= 1e-5, (rank, r)

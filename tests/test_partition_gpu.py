@@ -369,61 +369,6 @@ def test_exchange_hook_of_the_c_abi_drives_a_partitioned_hop(device):
     assert hop(0, cb0, 1, ys[0], rows=g.n_items + 1, rr=None) == -1
 
 
-class _ThreadComm:
-    """Stand-in for partition.Comm when the ranks of a partition are THREADS of one process sharing one GPU and one
-    stream: a collective = barrier, rank 0 sums the ranks' tensors on the device, barrier, every rank copies the sum.
-    All launches go to the same stream in the order the barriers impose, so no device synchronisation is needed."""
-
-    def __init__(self, rank, world, shared):
-        self.rank, self.world, self.shared = rank, world, shared
-
-    def _sum(self, t):
-        sh = self.shared
-        sh["slots"][self.rank] = t
-        sh["barrier"].wait()
-        if self.rank == 0:
-            total = sh["slots"][0].clone()
-            for other in sh["slots"][1:]:
-                total += other
-            sh["total"] = total
-        sh["barrier"].wait()
-        t.copy_(sh["total"])
-        sh["barrier"].wait()
-
-    def start(self, block):
-        self._sum(block)
-        return None
-
-    def wait(self, handle):
-        pass
-
-    def reduce_now(self, t):
-        self._sum(t)
-
-
-def _run_thread_ranks(world, fn):
-    import threading
-    shared = {"slots": [None] * world, "barrier": threading.Barrier(world), "total": None}
-    results, errors = [None] * world, []
-
-    def body(rank):
-        try:
-            torch.cuda.set_device(0)
-            results[rank] = fn(rank, _ThreadComm(rank, world, shared))
-        except BaseException as exc:                      # a failing rank must not leave the others at a barrier
-            errors.append((rank, exc))
-            shared["barrier"].abort()
-
-    threads = [threading.Thread(target=body, args=(r,)) for r in range(world)]
-    for t in threads:
-        t.start()
-    for t in threads:
-        t.join()
-    real = [e for e in errors if not isinstance(e[1], threading.BrokenBarrierError)]
-    assert not real, real
-    return results
-
-
 def test_eight_ranks_at_full_size_on_one_gpu(device):
     """BASELINE.json configs[3] and configs[4] with everything but RCCL: the 8-way partition of the full-size graph
     (1.64 M users x 54.6 k items, 20.3 M edges; D=64, K=3), its eight ranks as threads of this process on ONE GPU, every
@@ -507,7 +452,10 @@ def _eight_ranks_at_full_size(device, dim, layers, pick_share=None, monkeypatch=
                    w_items=rel(wp.detach()[nu:] - w0[nu:], ref_w[nu:] - w0[nu:]))
         return res
 
-    results = _run_thread_ranks(world, rank_body)
+    # imported here, not at the top: the support module imports the package, and the spawned ranks of this file set the
+    # package's environment knobs (``_init``) before they import it
+    from partition_edges_support import _run_thread_ranks      # the thread ranks and their ``_ThreadComm``
+    results = _run_thread_ranks(world, rank_body, device)
     torch.cuda.synchronize()
     print(f"eight ranks at D={dim} K={layers}: peak device memory {torch.cuda.max_memory_allocated(device) / 2 ** 30:.1f} GiB")
     for rank, r in enumerate(results):
