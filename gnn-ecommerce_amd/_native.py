@@ -205,6 +205,10 @@ SIGNATURES = {
     "lgc_sample_hard_triples": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_uint64,
                                         c_uint64, c_int32, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_void_p, c_void_p,
                                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "lgc_rank_positions_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int32]),
+    "lgc_rank_positions": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int32, c_void_p, c_void_p, c_int64,
+                                   c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                   c_size_t, c_void_p, c_void_p]),
 }
 
 
@@ -275,6 +279,7 @@ ATTR_MAX_TOP = 8       # LGC_ATTR_MAX_TOP
 NEIGHBORS_MAX_K = 64   # LGC_NEIGHBORS_MAX_K
 RERANK_MAX_CAND = 256  # LGC_RERANK_MAX_CAND
 HARDNEG_MAX_CAND = 256 # LGC_HARDNEG_MAX_CAND
+RANK_SEEN_MODES = {"zero": 0, "remove": 1}   # LGC_RANK_SEEN_ZERO, LGC_RANK_SEEN_REMOVE
 RERANK_ROUTES = {1: "lds", 2: "global"}   # lgc_rerank_route's codes (LGC_RERANK_ROUTE_*)
 
 

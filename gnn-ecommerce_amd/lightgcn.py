@@ -33,6 +33,7 @@ from .graph import get_graph
 from .lgconv import LGConv
 from .paths import shortest_paths
 from .similar import item_neighbors
+from .fullrank import evaluate_full_rank
 from .propagate import (DEFAULT_WORKSPACE_BYTES, TOPK_MAX, PositiveLists, RegHook, SeenLists, bpr_loss_fused, column_sums,
                         evaluate_ranking, evaluate_topk, mask_topk, pair_dot, propagate_sum, recommend_topk,
                         regularization_through, routable_index, scores_from_table)
@@ -252,6 +253,22 @@ class LightGCN(torch.nn.Module):
         if positives.ptr.device != ids.device:
             positives = positives.to(ids.device)
         return evaluate_ranking(user_t, item_t, seen, ids, positives, ks, workspace_bytes, coverage)
+
+    def evaluate_full_rank(self, edge_index, edge_weight, n_users, n_items, seen, users, positives, ks=(20,),
+                           seen_mode: str = "zero"):
+        """AUC, mean percentile rank, MRR and recall / hit rate at every K of ``ks`` (any K up to ``n_items``) from the exact
+        catalogue rank of every distinct held-out item; arguments as ``evaluate_metrics``.  ``seen_mode`` "zero" ranks as
+        ``recommendK`` does (a seen item competes with score * 0), "remove" takes the seen items out of the candidates.
+        Returns a ``fullrank.FullRankResult``.  One host sync at the end, plus the read of the number of pairs wherever
+        ``users`` is not the device tensor of the previous call (``fullrank.evaluate_full_rank``)."""
+        if not isinstance(positives, PositiveLists):
+            positives = PositiveLists.from_frame(positives, n_users)
+        if users is None:
+            users = positives.users
+        user_t, item_t, seen, ids = self._eval_tables(edge_index, edge_weight, n_users, n_items, seen, users)
+        if positives.ptr.device != ids.device:
+            positives = positives.to(ids.device)
+        return evaluate_full_rank(user_t, item_t, seen, ids, positives, ks, seen_mode)
 
     def recommendation_paths(self, edge_index, edge_weight, n_users, users, top_items, max_len: int = 7,
                              workspace_bytes: int = DEFAULT_WORKSPACE_BYTES, trace: Optional[list] = None):

@@ -1077,24 +1077,44 @@ class PositiveLists:
     def __init__(self, ptr: Tensor, items: Tensor, users: Tensor):
         self.ptr, self.items, self.users = ptr, items, users
         self._distinct: Optional[Tensor] = None
+        self._entries = None
+
+    def _sorted_entries(self):
+        """(owner, items, head) of all entries ordered by (user, item) -- two stable sorts -- with ``head`` marking the
+        first entry of every run of equal (user, item).  Temporaries: the callers keep what they derive, not these."""
+        dev, n_users = self.ptr.device, self.ptr.numel() - 1
+        owner = torch.repeat_interleave(torch.arange(n_users, device=dev), self.ptr[1:] - self.ptr[:-1],
+                                        output_size=self.items.numel())
+        items, order = torch.sort(self.items, stable=True)
+        owner, order = torch.sort(owner[order], stable=True)
+        items = items[order]
+        head = torch.ones_like(items, dtype=torch.bool)
+        head[1:] = (owner[1:] != owner[:-1]) | (items[1:] != items[:-1])
+        return owner, items, head
 
     @property
     def distinct(self) -> Tensor:
         """int64 [n_users]: the number of DISTINCT items of each user's list (0 for a user without one) -- what NDCG's
         ideal ranking and AP's denominator can at most reach, where recall divides by the length with duplicates.
         Computed once, on the lists' device (two stable sorts order the entries by (user, item); a run's head counts),
-        and kept."""
+        and kept; only the counts are."""
         if self._distinct is None:
-            dev, n_users = self.ptr.device, self.ptr.numel() - 1
-            owner = torch.repeat_interleave(torch.arange(n_users, device=dev), self.ptr[1:] - self.ptr[:-1],
-                                            output_size=self.items.numel())
-            items, order = torch.sort(self.items, stable=True)
-            owner, order = torch.sort(owner[order], stable=True)
-            items = items[order]
-            head = torch.ones_like(items, dtype=torch.bool)
-            head[1:] = (owner[1:] != owner[:-1]) | (items[1:] != items[:-1])
-            self._distinct = torch.bincount(owner[head], minlength=n_users).to(torch.int64).contiguous()
+            if self._entries is not None:
+                heads = self._entries[0]
+            else:
+                owner, _, head = self._sorted_entries()
+                heads = owner[head]
+            self._distinct = torch.bincount(heads, minlength=self.ptr.numel() - 1).to(torch.int64).contiguous()
         return self._distinct
+
+    def distinct_entries(self):
+        """(owner int64 [E], items int64 [E]): every distinct (user, item) of the lists, by user and then by item -- the
+        same sort ``distinct`` counts; user u's entries are [cumsum(distinct)[u - 1], cumsum(distinct)[u]).  Kept once
+        asked for (full-rank evaluation asks); ``distinct`` alone keeps no entry."""
+        if self._entries is None:
+            owner, items, head = self._sorted_entries()
+            self._entries = (owner[head].contiguous(), items[head].contiguous())
+        return self._entries
 
     @classmethod
     def from_lists(cls, user_id_idx, item_id_idx_list, n_users: int, device=None) -> "PositiveLists":

@@ -1099,6 +1099,62 @@ int lgc_sample_hard_triples(const int64_t *users, int64_t n,
                             int64_t *pos_out, int64_t *neg_out, float *neg_score, int32_t *neg_attempt,
                             int32_t *n_admissible, int32_t *status, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Full-rank evaluation (an addition to ABI 14: exports only): "where in the whole catalogue did this held-out purchase
+ * land?" -- per (user, item) pair the number of candidates that precede the item, which is what AUC, the mean percentile
+ * rank and recall at any K are made of.  lgc_mask_topk answers only for the first 256 places.  A counting problem over
+ * users x catalogue dot products: they run on the fp32 matrix cores (v_mfma_f32_16x16x4_f32) and end in integer counters in
+ * registers; no score is written to memory.  Upstream has no counterpart (src/lightgcn.py:165-190 stops at the top k).
+ *
+ *   users, user_stride, n_user_rows   fp32 [n_user_rows, dim], rows user_stride >= dim floats apart
+ *   items, item_stride, n_items       fp32 [n_items, dim], rows item_stride >= dim apart; n_items >= 1.  Columns at or past
+ *              dim are never read: a row may end there
+ *   pair_users, pair_items   int64 [n_pairs]: pair r = (u, p) asks for the place of item p in user u's ranking; any order,
+ *              repeats allowed.  A user outside [0, n_user_rows) or an item outside [0, n_items) sets LGC_ST_INDEX_OOB in
+ *              `status` and gives rank = n_equal = -1, n_cand = 0, value = 0; nothing is addressed through the id
+ *   seen_ptr, seen_items   int64 [n_user_rows + 1] and int64: a CSR over all users, read on trust as lgc_mask_topk reads
+ *              its lists; seen_ptr NULL = no lists, and seen_items is then ignored, its alignment too.  A user's items must be ascending (ingest.seen_csr, SeenLists.from_dense);
+ *              an entry equal to its predecessor is skipped, one outside [0, n_items) is ignored.  An unsorted list gives
+ *              unspecified counts but never an access out of range
+ *   seen_mode  LGC_RANK_SEEN_ZERO: every item is a candidate and a seen one competes with m = score * 0 (one rounded
+ *              multiply: +-0, and NaN for a seen +-inf) -- lgc_mask_topk's list form exactly, recommendK's ranking;
+ *              LGC_RANK_SEEN_REMOVE: the seen items are no candidates (the usual LightGCN protocol).  A pair whose p is
+ *              seen then gives rank = n_equal = -1 with n_cand and value (the raw score) still written and no status bit:
+ *              a property of the data, not an error.  Without lists the two modes coincide
+ *   slices     0 .. 64: the catalogue is cut into that many ranges of item tiles (128 items each), one workgroup per (tile
+ *              of 64 pairs, range); 0 = the library chooses (about 512 workgroups), a count above the number of item tiles
+ *              is clamped to it.  The result does not depend on it
+ *   rank       int32 [n_pairs]: the number of candidates i != p with precedes(i, p)
+ *   n_equal    int32 [n_pairs] or NULL: the number of candidates i != p whose key equals p's (degenerate ties show here)
+ *   n_cand     int32 [n_pairs] or NULL: the number of candidates, p counted
+ *   value      fp32 [n_pairs] or NULL: m(u, p)
+ *   workspace  device memory of at least lgc_rank_positions_workspace_bytes(n_pairs, n_items, slices) bytes, dword aligned.
+ *              The size function returns 0 for sizes the call would refuse and grows monotonically in n_pairs, n_items and
+ *              in slices over 1 .. 64
+ * Score: s(u, i) is lgc_score_rows' chain for the two rows -- fused multiply-adds over d ascending from +0, zeros past
+ * dim -- with its bits, except that a sum of -0 may come out as +0 in a comparison (the order does not tell them apart);
+ * `value` is the chain's own value.
+ * Order: lgc_mask_topk's total order on the masked score m -- every NaN (either sign bit) first, then +inf, the finite
+ * values descending with -0 = +0, then -inf; precedes(i, p): key(m_i) > key(m_p), or the keys are equal and i < p.  So in
+ * mode ZERO rank[r] is the column of p in lgc_mask_topk's row for u wherever that row is long enough.
+ * No float atomics; the slices add integers, whose sum does not depend on the order: the same bytes on every run.
+ * Errors before any launch: LGC_E_DIM (as lgc_dim_ok); LGC_E_INVAL (a null required pointer, a negative n_pairs or
+ * n_user_rows, a stride below dim, seen_mode outside {0, 1}, seen_ptr without seen_items); LGC_E_RANGE (slices outside
+ * 0 .. 64, n_items < 1, n_items, n_pairs or n_user_rows >= 2^31 - 1); LGC_E_ALIGN (an fp32 or int32 pointer or the workspace
+ * not dword aligned, an int64 pointer not 8-byte aligned); LGC_E_WORKSPACE (a workspace that is too small or missing).
+ * n_pairs == 0 validates, launches nothing and returns 0.
+ * ------------------------------------------------------------------------------------- */
+#define LGC_RANK_SEEN_ZERO   0
+#define LGC_RANK_SEEN_REMOVE 1
+size_t lgc_rank_positions_workspace_bytes(int64_t n_pairs, int64_t n_items, int32_t slices);
+int lgc_rank_positions(const float *users, int64_t user_stride, int64_t n_user_rows,
+                       const float *items, int64_t item_stride, int64_t n_items, int32_t dim,
+                       const int64_t *pair_users, const int64_t *pair_items, int64_t n_pairs,
+                       const int64_t *seen_ptr, const int64_t *seen_items, int32_t seen_mode,
+                       int32_t slices,
+                       int32_t *rank, int32_t *n_equal, int32_t *n_cand, float *value,
+                       void *workspace, size_t workspace_bytes, int32_t *status, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,11 +6,14 @@ backward -> Adam), then recommendK + MARK_MAPK on held-out purchases.  Data are 
 
     python tools/train_demo.py [--users 20000 --items 2000 --epochs 3 --dim 64 --layers 3]
     python tools/train_demo.py --hard-negatives 8 [--refresh 10]
+    python tools/train_demo.py --full-rank
 
 --hard-negatives M trains every triple against the hardest of M sampled negatives (TripleSampler.sample_hard; 0 = one
 uniform negative, the reference's batch_loader).  --refresh R scores them with the propagated table, recomputed every R
 steps; 0 scores them with the layer-0 table, which costs nothing.  The epoch line carries the mean attempt number of the
 negative (null without --hard-negatives: the uniform sampler does not report it) and the mean BPR gradient weight sigmoid(neg - pos): how much of a step is spent on gradients that matter.
+--full-rank adds AUC and MPR (the mean percentile rank) to the epoch line, from the exact catalogue rank of every held-out
+purchase (LightGCN.evaluate_full_rank, ranking as recommendK does): every held-out item counts, not only those in the top k.
 """
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -34,14 +37,19 @@ def latent_interactions(n_users, n_items, per_user, seed):
     return np.concatenate(users), np.concatenate(items)
 
 
-def main(argv=None):
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--users", type=int, default=20000); ap.add_argument("--items", type=int, default=2000)
     ap.add_argument("--per-user", type=int, default=12); ap.add_argument("--epochs", type=int, default=3)
     ap.add_argument("--dim", type=int, default=64); ap.add_argument("--layers", type=int, default=3)
     ap.add_argument("--batch", type=int, default=1024); ap.add_argument("--k", type=int, default=20)
     ap.add_argument("--hard-negatives", type=int, default=0, metavar="M"); ap.add_argument("--refresh", type=int, default=0, metavar="R")
-    args = ap.parse_args(argv)
+    ap.add_argument("--full-rank", action="store_true")
+    return ap.parse_args(argv)
+
+
+def main(argv=None):
+    args = parse_args(argv)
     dev = torch.device("cuda:0")
     u, i = latent_interactions(args.users, args.items, args.per_user, 0)
     rng = np.random.default_rng(1)
@@ -101,6 +109,11 @@ def main(argv=None):
                     f"R@{args.k}": float(recall), "batches": n_batch, "s": round(dt, 2),
                     "neg_attempt": float(torch.stack(attempts).mean().item()) if attempts else None,
                     "grad_weight": float(np.mean(weights))})
+        if args.full_rank:
+            with torch.no_grad():
+                full = model.evaluate_full_rank(edge_index, edge_weight, n_users, n_items, seen, list(test_pos["user_id_idx"]),
+                                                test_pos, ks=(args.k,))
+            log[-1].update({"AUC": full.mean["auc"], "MPR": full.mean["mpr"], f"full R@{args.k}": full.mean["recall"][0]})
         print(json.dumps(log[-1]), flush=True)
     sampler.check(); lg.check_index_status()
     return log
