@@ -723,8 +723,14 @@ int lgc_topk_coverage(const int64_t *topk, int64_t topk_stride, int32_t k, int64
  *                   by the row plan of lgc_spmm: rows of at most `short_max` entries by a lane group each, longer rows per
  *                   chunk of `chunks` (every longer row must be listed), one wavefront each; a row cut into several chunks
  *                   (slot >= 0) combines them with 64-bit atomic OR.  A row with (~seen[v] & active) == 0 -- `active` =
- *                   the mask of the batch's valid source bits -- is finished without reading its entries.  active == 0
- *                   launches nothing.  frontier_out must not be frontier_in.  The launch ADDS to `counters` (uint64 [4],
+ *                   the mask of the batch's valid source bits -- is finished without reading its entries: frontier_out[v]
+ *                   = 0, seen[v] unchanged.  Any other row gets all of `fresh`: it is masked by seen[v], not by `active`.
+ *                   A bit of frontier_in outside `active` therefore travels like any other, with one exception the caller
+ *                   must not rely on: a row cut into several chunks may drop such bits (a chunk that finds the row finished
+ *                   by a sibling chunk of the same level is skipped as well); bits inside `active`, and the count of new
+ *                   nodes, never depend on the cut or on timing.  paths.py keeps frontier_in inside `active`: a source
+ *                   outside the graph sets no bit.  Rows outside [row_begin, row_end) are neither read nor written.  active
+ *                   == 0 launches nothing.  frontier_out must not be frontier_in.  The launch ADDS to `counters` (uint64 [4],
  *                   zeroed by the caller): [0] += nodes newly reached, [2] |= their new bits, i.e. the sources whose
  *                   frontier is not empty after this level; [1] belongs to lgc_bfs_resolve, [3] is reserved.
  * lgc_bfs_resolve   for every pair (b, c) with dist[b, c] == LGC_BFS_UNSET (int32 [n_sources, n_targets], filled with it by
