@@ -20,6 +20,7 @@ from .sampler import TripleSampler
 from .similar import item_neighbors, row_rnorm
 from .fullrank import FullRankResult, PairRanks, evaluate_full_rank, positive_ranks
 from .rerank import list_diversity, mmr_rerank
+from .softmax import SoftmaxBatch, softmax_batch, softmax_from_table, softmax_loss_reference
 from . import ingest, serving
 from .trainer import PartitionedTrainer
 
@@ -29,4 +30,5 @@ __all__ = ["LightGCN", "BPRLoss", "LGConv", "PropGraph", "get_graph", "clear_cac
            "rank_metrics", "evaluate_ranking", "overlap_items", "metrics_frame", "RankingResult",
            "SessionLists", "fold_table", "fold_in", "Attribution", "attribute",
            "item_neighbors", "row_rnorm", "mmr_rerank", "list_diversity",
-           "positive_ranks", "evaluate_full_rank", "PairRanks", "FullRankResult"]
+           "positive_ranks", "evaluate_full_rank", "PairRanks", "FullRankResult",
+           "softmax_batch", "softmax_loss_reference", "softmax_from_table", "SoftmaxBatch"]

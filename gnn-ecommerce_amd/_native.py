@@ -209,6 +209,10 @@ SIGNATURES = {
     "lgc_rank_positions": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int32, c_void_p, c_void_p, c_int64,
                                    c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                    c_size_t, c_void_p, c_void_p]),
+    "lgc_softmax_workspace_bytes": (c_size_t, [c_int64, c_int64]),
+    "lgc_softmax_batch": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int32, c_void_p, c_int64, c_void_p, c_int64, c_void_p,
+                                  c_void_p, c_void_p, c_void_p, c_float, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                  c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_size_t, c_void_p, c_void_p]),
 }
 
 

@@ -19,6 +19,7 @@ the layer sum fused (``propagate.propagate_sum``) and pair scoring is one gather
 """
 from __future__ import annotations
 
+import math
 from typing import Optional, Union
 
 import torch
@@ -38,6 +39,7 @@ from .propagate import (DEFAULT_WORKSPACE_BYTES, TOPK_MAX, PositiveLists, RegHoo
                         evaluate_ranking, evaluate_topk, mask_topk, pair_dot, propagate_sum, recommend_topk,
                         regularization_through, routable_index, scores_from_table)
 from .rerank import check_lam, list_diversity, mmr_rerank
+from .softmax import ignore_lists, softmax_from_table
 
 RERANK_MAX_CAND = _native.RERANK_MAX_CAND
 
@@ -478,6 +480,53 @@ class LightGCN(torch.nn.Module):
     def recommendation_loss(self, pos_edge_rank: Tensor, neg_edge_rank: Tensor,
                             lambda_reg: float = 1e-4, **kwargs) -> Tensor:
         return BPRLoss(lambda_reg, **kwargs)(pos_edge_rank, neg_edge_rank, self.embedding.weight)
+
+    def softmax_loss(self, edge_index, edge_weight, users: Tensor, pos_items: Tensor, neg_items: Optional[Tensor] = None, *,
+                     temperature: float = 1.0, ignore=None, cand_bias: Optional[Tensor] = None) -> Tensor:
+        """In-batch softmax (InfoNCE / sampled-softmax) loss of a batch, an addition to the reference's BPR: every user
+        of ``users`` is scored against ALL candidates ``cat[pos_items, neg_items]`` (or ``pos_items`` alone) and
+        ``loss = (1 / B) sum_i log sum_{j in J_i} exp((s_ij - s_ii) / temperature)``, where ``J_i`` holds the user's own
+        positive (column i) and every other candidate that is not the same item and not in the user's ignore list.  With
+        ``neg_items`` that is up to ``2B - 1`` negatives per positive from the rows the BPR step propagates anyway.
+
+        ``users``, ``pos_items``, ``neg_items``: int64 ``[B]`` node ids as ``TripleSampler.sample()`` returns them (items
+        already offset by ``n_users``).  ``ignore``: a ``TripleSampler`` or its ``(ign_ptr, ign_items)`` pair -- a user's
+        other positives among the candidates are then no negatives; None admits every other item.  ``cand_bias``: fp32
+        ``[C]`` added to the logits of a column (``-log q_j`` corrects for the sampling distribution).  ``temperature``
+        must be finite and > 0.  For ``B = 1, C = 2, temperature = 1`` the value is BPR's ``softplus(neg - pos)``.
+
+        With gradients on this is one autograd node with a sparse backward (``softmax.softmax_from_table``), and
+        ``regularization_loss(users, pos, neg, decay)`` after it routes its gradient into that node exactly as after
+        ``forward``.  Single device; ``PartitionedTrainer`` keeps BPR."""
+        if isinstance(temperature, bool) or not isinstance(temperature, (int, float)) or not math.isfinite(temperature) \
+                or not temperature > 0:
+            raise ValueError(f"temperature must be a finite number > 0, got {temperature!r}")
+        lists = [users, pos_items] + ([neg_items] if neg_items is not None else [])
+        for name, t in zip(("users", "pos_items", "neg_items"), lists):
+            if not torch.is_tensor(t) or t.dtype != torch.int64 or t.dim() != 1:
+                raise TypeError(f"{name} must be a 1-D int64 tensor of node ids")
+            if t.numel() != users.numel():
+                raise ValueError(f"{name} has {t.numel()} entries, users {users.numel()}")
+        if users.numel() == 0:
+            raise ValueError("an empty batch has no loss")
+        ignore = ignore_lists(ignore)
+        if cand_bias is not None and (not torch.is_tensor(cand_bias) or cand_bias.dtype != torch.float32 or cand_bias.dim() != 1
+                                      or cand_bias.numel() != len(lists[1:]) * users.numel()):
+            raise TypeError("cand_bias must be a 1-D float32 tensor with one value per candidate")
+        x0 = self.embedding.weight
+        _native.require_device(x0, "LightGCN.embedding.weight")
+        normalize = self.convs[0].normalize if self.num_layers > 0 else True
+        graph = get_graph(edge_index, edge_weight, self.num_nodes, normalize)
+        if graph.split is None:
+            raise ValueError("softmax_loss needs a user|item (bipartite) graph with the users first")
+        b = users.numel()
+        cands = pos_items if neg_items is None else torch.cat([pos_items, neg_items])
+        target = torch.arange(b, dtype=torch.int32, device=users.device)
+        hook = RegHook(x0) if (torch.is_grad_enabled() and x0.requires_grad) else None
+        loss = softmax_from_table(x0, graph, self._alphas(), users, cands, target, ignore, 1.0 / float(temperature), b,
+                                  cand_bias, hook)
+        x0._lgcn_reg_hook = hook if (hook is not None and hook.token is not None) else None
+        return loss
 
     def regularization_loss(self, users: Tensor, pos_items: Tensor, neg_items: Tensor, decay: float,
                             batch_size: Optional[int] = None) -> Tensor:

@@ -1161,6 +1161,73 @@ int lgc_rank_positions(const float *users, int64_t user_stride, int64_t n_user_r
                        int32_t *rank, int32_t *n_equal, int32_t *n_cand, float *value,
                        void *workspace, size_t workspace_bytes, int32_t *status, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * In-batch softmax loss (an addition to ABI 14: exports only): a softmax (InfoNCE / sampled-softmax) objective over many
+ * negatives per positive, for the rows a training batch has propagated anyway.  Every one of n_rows user rows is scored
+ * against every one of n_cand listed items on the fp32 matrix cores (v_mfma_f32_16x16x4_f32); a user's own other positives
+ * are no negatives (the sampler's ignore lists); out come the loss, the gradient of the logits and its two products with the
+ * table rows, which are the gradient with respect to the propagated rows -- the seed of the sparse backward.  Five launches
+ * in stream order.  Upstream trains BPR on one negative (src/train_lightgcn.py:137-147) and has no counterpart.
+ *
+ *   table, stride, table_rows, split, dim   fp32 [table_rows, dim], rows stride >= dim floats apart: the propagated table,
+ *              user rows [0, split), item rows [split, table_rows).  Columns at or past dim are never read: a row may end there
+ *   row_users  int64 [n_rows]: node ids in [0, split);  cand_items int64 [n_cand]: node ids in [split, table_rows), repeats
+ *              allowed;  target int32 [n_rows]: the column of row i's positive
+ *   ign_ptr, ign_items   int32 [split + 1] and int64: TripleSampler's ignore lists (node ids, ascending per user), read on
+ *              trust as lgc_sample_triples reads them; both NULL = every list is empty
+ *   cand_bias  fp32 [n_cand] or NULL: added to every logit of a column (-log q_j corrects for the sampling distribution)
+ *   inv_tau    1 / temperature, finite and > 0;  size: the GLOBAL batch size, as in lgc_bpr_loss
+ *   loss       fp32 [1];  row_loss fp32 [n_rows] or NULL;  n_adm int32 [n_rows] or NULL
+ *   grad_logits, g_stride   fp32 [n_rows, n_cand], rows g_stride >= n_cand apart, or NULL (G then lives in the workspace)
+ *   grad_users, grad_cands, grad_stride   fp32 [n_rows, dim] and [n_cand, dim], rows grad_stride >= dim apart.  Columns past
+ *              dim of a gradient row are never written
+ *   workspace  device memory of at least lgc_softmax_workspace_bytes(n_rows, n_cand) bytes, dword aligned (needed whether or
+ *              not grad_logits is given).  The size function returns 0 for sizes the call would refuse and grows
+ *              monotonically in both arguments
+ * Logit.  s_ij = dot(table[row_users[i]], table[cand_items[j]]) is lgc_score_rows' chain for the two rows -- fp32 fused
+ * multiply-adds over d ascending from +0, zeros past dim -- with its bits (a sum of -0 may come out as +0, which no result
+ * here tells apart); z_ij = s_ij * inv_tau, one rounded multiply, then + cand_bias[j], one rounded add.
+ * Admissible set.  With t = target[i], J_i holds t and every j != t whose cand_items[j] is a valid item id, differs from
+ * cand_items[t] and is not in the ignore list of user row_users[i].
+ * Results.  m_i = max_{J_i} z_ij;  S_i = sum_{J_i} exp(z_ij - m_i);  loss_i = (m_i - z_it) + log S_i, which is
+ * log sum_{J_i} exp(z_ij - z_it);  *loss = (sum_i loss_i) / size, one fixed-order sum;  p_ij = exp(z_ij - m_i) / S_i;
+ * G_ij = (p_ij - [j = t]) * (inv_tau / size) for j in J_i and exactly +0 for every other j;  grad_users[i] = sum_j G_ij
+ * table[cand_items[j]];  grad_cands[j] = sum_i G_ij table[row_users[i]], both on the matrix cores with ONE accumulator per
+ * element that takes the inner extent in ascending order;  n_adm[i] = |J_i| - 1.  A row with J_i = {t} has loss_i = +0 and a
+ * zero row of G.  No float atomics: every output depends on the arguments alone, never on the run.
+ * Bad ids.  A row whose user is outside [0, split), whose target is outside [0, n_cand) or whose cand_items[target] is no
+ * item is invalid: loss_i = 0, n_adm = 0, zero rows of G and grad_users.  A candidate outside [split, table_rows) is
+ * admissible for nobody and its grad_cands row is zeros.  Either sets LGC_ST_INDEX_OOB in `status`; every id is range-checked
+ * before an address is formed from it.
+ * Non-finite values.  z = -inf contributes 0 (a row whose admissible logits are ALL -inf gives NaN; a target at -inf beside
+ * finite logits gives loss_i = +inf).  A NaN or +inf among a row's admissible logits gives NaN in row_loss[i], in every
+ * admissible element of row i of G (the others stay +0), in grad_users[i] and in *loss, as a float64 evaluation of the
+ * max-subtracted formula gives; n_adm is unaffected.  Such a row changes no other row's row_loss, G or grad_users; it does put
+ * NaN into grad_cands[j] for every j it admits.  (A non-finite TABLE row of a candidate reaches every row's grad_users
+ * through 0 * NaN, as in the float64 product.)
+ * Every output element is written -- except with n_rows == 0 or n_cand == 0, which validates, writes *loss = 0, launches
+ * nothing else and returns 0.
+ * Errors before any launch: LGC_E_DIM (as lgc_dim_ok); LGC_E_INVAL (a null required pointer -- table, row_users, cand_items,
+ * target, loss, grad_users, grad_cands, status --, exactly one of ign_ptr and ign_items, a negative n_rows, n_cand or
+ * table_rows, size < 1, stride or grad_stride below dim, g_stride below n_cand, inv_tau not finite or <= 0, split outside
+ * [0, table_rows]); LGC_E_RANGE (n_rows, n_cand or table_rows >= 2^31, or n_cand above 65535 * 128: the panel then stays
+ * below 2^54 floats and the workspace arithmetic cannot overflow);
+ * LGC_E_ALIGN (an fp32 or int32 pointer or the workspace not dword aligned, an int64 pointer not 8-byte aligned);
+ * LGC_E_WORKSPACE (a workspace that is too small or missing).
+ * ------------------------------------------------------------------------------------- */
+size_t lgc_softmax_workspace_bytes(int64_t n_rows, int64_t n_cand);
+int lgc_softmax_batch(const float *table, int64_t stride, int64_t table_rows, int64_t split, int32_t dim,
+                      const int64_t *row_users, int64_t n_rows,
+                      const int64_t *cand_items, int64_t n_cand,
+                      const int32_t *target,
+                      const int32_t *ign_ptr, const int64_t *ign_items,
+                      const float *cand_bias,
+                      float inv_tau, int64_t size,
+                      float *loss, float *row_loss, int32_t *n_adm,
+                      float *grad_logits, int64_t g_stride,
+                      float *grad_users, float *grad_cands, int64_t grad_stride,
+                      void *workspace, size_t workspace_bytes, int32_t *status, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,6 +7,7 @@ backward -> Adam), then recommendK + MARK_MAPK on held-out purchases.  Data are 
     python tools/train_demo.py [--users 20000 --items 2000 --epochs 3 --dim 64 --layers 3]
     python tools/train_demo.py --hard-negatives 8 [--refresh 10]
     python tools/train_demo.py --full-rank
+    python tools/train_demo.py --loss softmax [--temperature 0.2]
 
 --hard-negatives M trains every triple against the hardest of M sampled negatives (TripleSampler.sample_hard; 0 = one
 uniform negative, the reference's batch_loader).  --refresh R scores them with the propagated table, recomputed every R
@@ -14,6 +15,10 @@ steps; 0 scores them with the layer-0 table, which costs nothing.  The epoch lin
 negative (null without --hard-negatives: the uniform sampler does not report it) and the mean BPR gradient weight sigmoid(neg - pos): how much of a step is spent on gradients that matter.
 --full-rank adds AUC and MPR (the mean percentile rank) to the epoch line, from the exact catalogue rank of every held-out
 purchase (LightGCN.evaluate_full_rank, ranking as recommendK does): every held-out item counts, not only those in the top k.
+--loss softmax trains with the in-batch softmax loss (LightGCN.softmax_loss) instead of BPR: every user
+of a batch against all 2B sampled items at --temperature, a user's other purchases masked out through the sampler's ignore
+lists, the regulariser routed into the same node.  The epoch line then carries "softmax" (the mean loss) in place of "bpr" and
+"grad_weight".  It combines with --hard-negatives (the hard negative is one more candidate for everyone) and --full-rank.
 """
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -45,6 +50,7 @@ def parse_args(argv=None):
     ap.add_argument("--batch", type=int, default=1024); ap.add_argument("--k", type=int, default=20)
     ap.add_argument("--hard-negatives", type=int, default=0, metavar="M"); ap.add_argument("--refresh", type=int, default=0, metavar="R")
     ap.add_argument("--full-rank", action="store_true")
+    ap.add_argument("--loss", choices=["bpr", "softmax"], default="bpr"); ap.add_argument("--temperature", type=float, default=0.2)
     return ap.parse_args(argv)
 
 
@@ -90,6 +96,12 @@ def main(argv=None):
             else:
                 users, pos, neg = sampler.sample(args.batch)
             step += 1
+            if args.loss == "softmax":
+                loss = model.softmax_loss(edge_index, edge_weight, users, pos, neg, temperature=args.temperature, ignore=sampler)
+                (loss + model.regularization_loss(users, pos, neg, 1e-4)).backward()
+                opt.step()
+                losses.append(loss.item())
+                continue
             labels = torch.stack((torch.cat([users, users]), torch.cat([pos, neg])))
             out = model(edge_index, labels, edge_weight)
             size = len(users)
@@ -108,7 +120,10 @@ def main(argv=None):
         log.append({"epoch": epoch, "bpr": float(np.mean(losses)), f"P@{args.k}": float(precision),
                     f"R@{args.k}": float(recall), "batches": n_batch, "s": round(dt, 2),
                     "neg_attempt": float(torch.stack(attempts).mean().item()) if attempts else None,
-                    "grad_weight": float(np.mean(weights))})
+                    "grad_weight": float(np.mean(weights)) if weights else None})
+        if args.loss == "softmax":
+            log[-1] = {"epoch": epoch, "softmax": log[-1].pop("bpr"), "temperature": args.temperature,
+                       **{k: v for k, v in log[-1].items() if k not in ("epoch", "grad_weight")}}
         if args.full_rank:
             with torch.no_grad():
                 full = model.evaluate_full_rank(edge_index, edge_weight, n_users, n_items, seen, list(test_pos["user_id_idx"]),
