@@ -30,15 +30,9 @@ struct AttrArgs {
     int32_t groups, es;             // float4 groups of a row (ceil(dim / 4)); LDS row stride in floats
 };
 
-// lgc_mask_topk's total order (lgconv_serve.hip): ascending with the value, every NaN the one top key, -0 = +0
-__device__ __forceinline__ uint32_t order_key(float v) {
-    const float w = __fadd_rn(v, 0.0f);
-    const uint32_t u = __float_as_uint(w);
-    const uint32_t key = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-    return w != w ? 0xFFFFFFFFu : key;
-}
-
-// four floats of a table row from column d; columns >= dim read as 0 and are never touched
+// Four floats of a table row from column d; columns >= dim read as 0 and are never touched: what load4 of lgconv_common.h
+// gives, but dword by dword where the rows are not 16-byte aligned.  Kept: load4<false>'s one overlapping 16-byte load is
+// other code for k_attribute<false>, and that has not been timed.
 template <bool VEC>
 __device__ __forceinline__ f4 attr_load4(const float *__restrict__ row, int d, int dim) {
     f4 v = {0.0f, 0.0f, 0.0f, 0.0f};
@@ -53,15 +47,12 @@ __device__ __forceinline__ f4 attr_load4(const float *__restrict__ row, int d, i
     return v;
 }
 
-// lgc_score_rows' chain: v_fma over d = 0 .. 4 * groups - 1 ascending from +0, `a` the user-side row, `b` the item row
+// lgc_score_rows' chain (score_chain) over the whole staged rows, `a` the user-side row, `b` the item row
 __device__ __forceinline__ float attr_dot(const float *a, const float *b, int groups) {
     float acc = 0.0f;
     for (int g = 0; g < groups; ++g) {
         const f4 x = *reinterpret_cast<const f4 *>(a + 4 * g), y = *reinterpret_cast<const f4 *>(b + 4 * g);
-        acc = __fmaf_rn(x.x, y.x, acc);
-        acc = __fmaf_rn(x.y, y.y, acc);
-        acc = __fmaf_rn(x.z, y.z, acc);
-        acc = __fmaf_rn(x.w, y.w, acc);
+        acc = score_chain(x, y, acc);
     }
     return acc;
 }
@@ -342,8 +333,6 @@ __global__ __launch_bounds__(kBlock) void k_attribute(const AttrArgs p) {
     }
 }
 
-bool aligned_to(const void *p, size_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
-
 unsigned long long lds_ok_attr[2];
 
 }  // namespace
@@ -385,10 +374,8 @@ int lgc_attribute(const lgc_attr_args *args, void *stream_) {
     void (*kern)(const AttrArgs) = vec ? k_attribute<true> : k_attribute<false>;
     const size_t lds = sizeof(float) * ((size_t)(a.n_targets + 1 + kAttrBatch) * p.es + (size_t)kAttrBatch * a.n_targets) +
                        sizeof(int32_t) * (64 + 6 * kAttrBatch + 4);
-    if (lds > 64 * 1024) {
-        const int rc_attr = allow_big_lds(reinterpret_cast<const void *>(kern), 112 * 1024, &lds_ok_attr[vec ? 1 : 0]);
-        if (rc_attr != 0) return rc_attr;
-    }
+    const int rc_attr = allow_lds(reinterpret_cast<const void *>(kern), lds, 64 * 1024, 112 * 1024, &lds_ok_attr[vec ? 1 : 0]);
+    if (rc_attr != 0) return rc_attr;
     hipLaunchKernelGGL(kern, dim3((unsigned)a.n_rows), dim3(kBlock), lds, as_stream(stream_), p);
     return (int)hipGetLastError();
 }

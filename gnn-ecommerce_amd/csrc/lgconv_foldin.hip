@@ -180,8 +180,6 @@ __global__ __launch_bounds__(kBlock) void k_fold_in(const FoldArgs p) {
     }
 }
 
-bool aligned_to(const void *p, size_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
-
 }  // namespace
 
 extern "C" {

@@ -6,8 +6,6 @@
 
 namespace {
 
-typedef unsigned long long u64;
-
 // Geometry.  A workgroup is four wavefronts, each with a sample of its own; they share nothing but
 // the one barrier behind the staging of their user rows.  Round r of a sample gives attempt 64 r + lane + 1 to every lane:
 // the lane draws its node, binary-searches the user's ignore set, and a ballot with a prefix popcount keeps the first
@@ -39,54 +37,9 @@ struct HnArgs {
     int32_t n, n_users, n_items, n_cand, dim;
 };
 
-// the sampler's stream (lgconv_serve.hip: k_sample_triples; tests/sampler_support.py restates it)
-__device__ __forceinline__ u64 hn_mix64(u64 z) {
-    z += 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
-__device__ __forceinline__ u64 hn_bounded(u64 r, u64 range) { return __umul64hi(r, range); }
-
-// lgc_mask_topk's total order (lgconv_serve.hip): ascending with the value, every NaN the one top key, -0 = +0
-__device__ __forceinline__ uint32_t hn_order_key(float v) {
-    const float w = __fadd_rn(v, 0.0f);
-    const uint32_t u = __float_as_uint(w);
-    const uint32_t key = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-    return w != w ? 0xFFFFFFFFu : key;
-}
-
-__device__ __forceinline__ u64 hn_wave_max(u64 v) {
-#pragma unroll
-    for (int m = kWave / 2; m > 0; m >>= 1) {
-        const u64 o = __shfl_xor(v, m, kWave);
-        v = o > v ? o : v;
-    }
-    return v;
-}
-
-// Four floats of a table row starting at column d (d % 4 == 0).  VEC: the width is a multiple of 4 and every row starts on
-// 16 bytes, one aligned 16-byte load.  Otherwise dwords: columns >= dim read as 0 and are never touched (the row may end
-// there: padding columns, the next row, or the end of the allocation).
-template <bool VEC>
-__device__ __forceinline__ f4 hn_load4(const float *__restrict__ row, int d, int dim) {
-    if (VEC) return *reinterpret_cast<const f4 *>(row + d);
-    f4 v = {0.0f, 0.0f, 0.0f, 0.0f};
-    if (d + 4 <= dim) {
-        v = *reinterpret_cast<const f4u *>(row + d);
-    } else {
-        if (d + 0 < dim) v.x = row[d + 0];
-        if (d + 1 < dim) v.y = row[d + 1];
-        if (d + 2 < dim) v.z = row[d + 2];
-    }
-    return v;
-}
-
-// dot(user row, item row) of a live lane, +0 in the others: lgc_score_rows' chain -- v_fma over d = 0 .. groups * 4 - 1
-// ascending from +0, zeros past dim, the user's value the first factor.  `ur` is the staged user row in LDS, zero-filled to
-// a multiple of 4; kHnBatch loads of the lane's row are issued before the first is consumed.  No step runs past
-// groups * 4: fma(0, 0, -0) is +0, an extra step could change a sign.
+// dot(user row, item row) of a live lane, +0 in the others: lgc_score_rows' chain (score_chain), the user's value the first
+// factor.  `ur` is the staged user row in LDS, zero-filled to a multiple of 4; kHnBatch loads of the lane's row are issued
+// before the first is consumed.
 template <bool VEC>
 __device__ __forceinline__ float hn_dot(const float *ur, const float *__restrict__ row, int dim, int groups, bool live) {
     float acc = 0.0f;
@@ -95,15 +48,12 @@ __device__ __forceinline__ float hn_dot(const float *ur, const float *__restrict
             f4 b[kHnBatch];
 #pragma unroll
             for (int j = 0; j < kHnBatch; ++j)
-                if (g0 + j < groups) b[j] = hn_load4<VEC>(row, 4 * (g0 + j), dim);
+                if (g0 + j < groups) b[j] = load4<VEC>(row, 4 * (g0 + j), dim);
 #pragma unroll
             for (int j = 0; j < kHnBatch; ++j) {
                 if (g0 + j < groups) {
                     const f4 a = *reinterpret_cast<const f4 *>(ur + 4 * (g0 + j));
-                    acc = __fmaf_rn(a.x, b[j].x, acc);
-                    acc = __fmaf_rn(a.y, b[j].y, acc);
-                    acc = __fmaf_rn(a.z, b[j].z, acc);
-                    acc = __fmaf_rn(a.w, b[j].w, acc);
+                    acc = score_chain(a, b[j], acc);
                 }
             }
         }
@@ -144,10 +94,10 @@ __global__ __launch_bounds__(kBlock) void k_sample_hard(const HnArgs p) {
         return;
     }
     const float *ur = hn_user[wv];
-    const u64 key = hn_mix64(hn_mix64(p.seed) ^ hn_mix64(p.step * 0xD1B54A32D192ED03ull + (u64)i));
+    const u64 key = mix64(mix64(p.seed) ^ mix64(p.step * 0xD1B54A32D192ED03ull + (u64)i));
     if (lane == 0) {
         const int32_t pb = p.pos_ptr[u], pc = p.pos_ptr[u + 1] - pb;
-        p.pos_out[i] = p.pos_items[pb + (int64_t)hn_bounded(hn_mix64(key), (u64)pc)];
+        p.pos_out[i] = p.pos_items[pb + (int64_t)bounded(mix64(key), (u64)pc)];
     }
     const int32_t ib = p.ign_ptr[u], ie = p.ign_ptr[u + 1];
 
@@ -158,21 +108,16 @@ __global__ __launch_bounds__(kBlock) void k_sample_hard(const HnArgs p) {
     int best_item = 0, taken = 0, item = 0;
     for (int r = 0; r < kHnRounds && taken < p.n_cand; ++r) {
         const int attempt = r * kWave + lane + 1;
-        item = (int)hn_bounded(hn_mix64(key + 0x632BE59BD9B4E019ull * (u64)attempt), (u64)p.n_items);
+        item = (int)bounded(mix64(key + 0x632BE59BD9B4E019ull * (u64)attempt), (u64)p.n_items);
         const int64_t node = (int64_t)p.n_users + item;
-        int32_t lo = ib, hi = ie;                            // binary search in the sorted ignore set
-        while (lo < hi) {
-            const int32_t mid = lo + ((hi - lo) >> 1);
-            if (p.ign_items[mid] < node) lo = mid + 1; else hi = mid;
-        }
-        const bool admissible = !(lo < ie && p.ign_items[lo] == node);
+        const bool admissible = !in_sorted(p.ign_items, ib, ie, node);
         const u64 mask = __ballot(admissible);
         const int before = __popcll(mask & ((1ull << lane) - 1ull));
         const bool keep = admissible && taken + before < p.n_cand;
         taken = min(p.n_cand, taken + __popcll(mask));
         const float score = hn_dot<VEC>(ur, p.item_table + (int64_t)item * p.item_stride, p.dim, groups, keep);
-        const u64 mine = keep ? ((u64)hn_order_key(score) << 32) | (uint32_t)~(uint32_t)attempt : 0ull;
-        const u64 top = hn_wave_max(mine);
+        const u64 mine = keep ? ((u64)order_key(score) << 32) | (uint32_t)~(uint32_t)attempt : 0ull;
+        const u64 top = wave_max(mine);
         if (top > best) {                                    // the same for every lane
             const int src = (int)(~(uint32_t)top - 1u) & (kWave - 1);
             best = top;
@@ -237,7 +182,7 @@ int lgc_sample_hard_triples(const int64_t *users, int64_t n, const int32_t *pos_
     p.n_items = (int32_t)n_items;
     p.n_cand = n_cand;
     p.dim = dim;
-    const bool vec = dim % 4 == 0 && item_stride % 4 == 0 && reinterpret_cast<uintptr_t>(item_table) % 16 == 0;
+    const bool vec = dim % 4 == 0 && item_stride % 4 == 0 && aligned_to(item_table, 16);
     hipLaunchKernelGGL(vec ? k_sample_hard<true> : k_sample_hard<false>, dim3(ceil_div(n, kHnRows)), dim3(kBlock), 0,
                        as_stream(stream_), p);
     return (int)hipGetLastError();

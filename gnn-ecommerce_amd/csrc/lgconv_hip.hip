@@ -56,12 +56,7 @@ __global__ void k_build_rowptr(const int32_t *__restrict__ sorted_keys, int32_t 
                                int32_t *__restrict__ rowptr) {
     int32_t r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r > n_nodes) return;
-    int32_t lo = 0, hi = n_edges;  // first position whose key >= r
-    while (lo < hi) {
-        int32_t mid = lo + ((hi - lo) >> 1);
-        if (sorted_keys[mid] < r) lo = mid + 1; else hi = mid;
-    }
-    rowptr[r] = lo;
+    rowptr[r] = lower_bound(sorted_keys, 0, n_edges, r);   // first position whose key >= r
 }
 
 __global__ void k_build_sorted_weight(const int32_t *__restrict__ perm, const float *__restrict__ w,
@@ -1731,8 +1726,6 @@ int dispatch_dim(const DimCfg &cfg, F &&f) {
     if (cfg.vec == 4) return f(std::integral_constant<int, 4>{});
     return f(std::integral_constant<int, 1>{});
 }
-
-bool aligned_to(const void *p, size_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
 
 // The table triple of a hop entry point -- x gathered, y written, r the optional epilogue term (r_stride counts only with
 // r) -- as rows of `dim` floats, `stride` floats apart: LGC_E_INVAL for a missing table or a stride below the width,

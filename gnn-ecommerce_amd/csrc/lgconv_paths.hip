@@ -13,12 +13,6 @@ typedef int e2 __attribute__((ext_vector_type(2)));
 constexpr int kBfsGroup = 8;                     // lanes per short row: eight 8-byte entries = one 64-byte line per step
 constexpr int kBfsRowsPerBlock = kBlock / kBfsGroup;
 
-__device__ __forceinline__ uint64_t wave_or(uint64_t v) {
-#pragma unroll
-    for (int off = 1; off < kWave; off <<= 1) v |= __shfl_xor(v, off);
-    return v;
-}
-
 // What a wavefront reports for a level: nodes newly reached (counters[0]: `newly` is set by the lane that speaks for
 // such a node) and the OR of the bits published (counters[2] = the sources whose frontier is not empty).  At most one
 // atomic per counter word and wavefront.

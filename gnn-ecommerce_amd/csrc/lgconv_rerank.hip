@@ -5,8 +5,6 @@
 
 namespace {
 
-typedef unsigned long long u64;
-
 // Geometry.  Every wavefront owns one row of candidates, so the argmax of a step and the hand-out
 // of the chosen row are cross-lane operations without a barrier; a workgroup is ONE wavefront, so that as many rows are
 // resident on a CU as their staged candidates leave room for (five at D = 64, N = 100).  Lane l owns
@@ -49,40 +47,6 @@ struct RrArgs {
     float lambda, oml;
     RrCuts cuts;
 };
-
-// lgc_mask_topk's total order (lgconv_serve.hip): ascending with the value, every NaN the one top key, -0 = +0
-__device__ __forceinline__ uint32_t rr_order_key(float v) {
-    const float w = __fadd_rn(v, 0.0f);
-    const uint32_t u = __float_as_uint(w);
-    const uint32_t key = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-    return w != w ? 0xFFFFFFFFu : key;
-}
-
-__device__ __forceinline__ float rr_key_value(uint32_t key) {
-    return __uint_as_float((key & 0x80000000u) ? (key & 0x7FFFFFFFu) : ~key);
-}
-
-__device__ __forceinline__ u64 rr_wave_max(u64 v) {
-#pragma unroll
-    for (int m = kWave / 2; m > 0; m >>= 1) {
-        const u64 o = __shfl_xor(v, m, kWave);
-        v = o > v ? o : v;
-    }
-    return v;
-}
-
-// Four floats of a table row starting at column d (d % 4 == 0); columns >= dim read as 0 and are never touched.
-__device__ __forceinline__ f4 rr_load4(const float *__restrict__ row, int d, int dim) {
-    f4 v = {0.0f, 0.0f, 0.0f, 0.0f};
-    if (d + 4 <= dim) {
-        v = *reinterpret_cast<const f4u *>(row + d);
-    } else {
-        if (d + 0 < dim) v.x = row[d + 0];
-        if (d + 1 < dim) v.y = row[d + 1];
-        if (d + 2 < dim) v.z = row[d + 2];
-    }
-    return v;
-}
 
 // What a row's wavefront keeps of its positions, and where their item rows are read from.
 template <bool STAGED>
@@ -137,7 +101,7 @@ struct RrRow {
                         const int it = ids_w[row];
                         if (it >= 0) {
                             dst[i] = row * p.ls + 4 * g;
-                            v[i] = rr_load4(p.items + (int64_t)it * p.item_stride, 4 * g, p.dim);
+                            v[i] = load4<false>(p.items + (int64_t)it * p.item_stride, 4 * g, p.dim);
                         }
                     }
                 }
@@ -153,8 +117,8 @@ struct RrRow {
         return STAGED ? rows + (size_t)pos * p.ls : p.items + (int64_t)ids[pos] * p.item_stride;
     }
 
-    // acc[s] = dot(row of position lane + 64 s, rc) for the slots of `live`, the others are left at +0: lgc_score_rows' chain,
-    // fused multiply-adds over d ascending from +0 with zeros past dim.  The slots' chains are independent of each other.
+    // acc[s] = dot(row of position lane + 64 s, rc) for the slots of `live`, the others are left at +0: lgc_score_rows' chain
+    // (score_chain).  The slots' chains are independent of each other.
     __device__ __forceinline__ void dots(const RrArgs &p, const float *rc, uint32_t live, int nslots, float (&acc)[kRrSlots]) const {
         const float *rp[kRrSlots];
 #pragma unroll
@@ -164,15 +128,12 @@ struct RrRow {
         }
 #pragma unroll 4
         for (int d = 0; d < p.dim; d += 4) {
-            const f4 cv = STAGED ? *reinterpret_cast<const f4 *>(rc + d) : rr_load4(rc, d, p.dim);
+            const f4 cv = STAGED ? *reinterpret_cast<const f4 *>(rc + d) : load4<false>(rc, d, p.dim);
 #pragma unroll
             for (int s = 0; s < kRrSlots; ++s) {
                 if (s < nslots) {
-                    const f4 a = STAGED ? *reinterpret_cast<const f4 *>(rp[s] + d) : rr_load4(rp[s], d, p.dim);
-                    acc[s] = __fmaf_rn(a.x, cv.x, acc[s]);
-                    acc[s] = __fmaf_rn(a.y, cv.y, acc[s]);
-                    acc[s] = __fmaf_rn(a.z, cv.z, acc[s]);
-                    acc[s] = __fmaf_rn(a.w, cv.w, acc[s]);
+                    const f4 a = STAGED ? *reinterpret_cast<const f4 *>(rp[s] + d) : load4<false>(rp[s], d, p.dim);
+                    acc[s] = score_chain(a, cv, acc[s]);
                 }
             }
         }
@@ -208,17 +169,17 @@ __global__ __launch_bounds__(kRrBlock) void k_rerank_mmr(const RrArgs p) {
         for (int s = 0; s < kRrSlots; ++s) {
             if ((open >> s) & 1u) {
                 const float obj = t == 0 ? lrel[s] : __fsub_rn(lrel[s], __fmul_rn(p.oml, pen[s]));
-                const u64 key = ((u64)rr_order_key(obj) << 32) | (uint32_t)~(uint32_t)(lane + kWave * s);
+                const u64 key = ((u64)order_key(obj) << 32) | (uint32_t)~(uint32_t)(lane + kWave * s);
                 best = key > best ? key : best;
             }
         }
-        best = rr_wave_max(best);
+        best = wave_max(best);
         const int c = best ? (int)~(uint32_t)best : -1;      // the same for every lane
         if (lane == 0) {
             const int64_t o = r * k + t;
             p.out_index[o] = c >= 0 ? (int64_t)row.ids[c] : -1;
             if (p.out_pos) p.out_pos[o] = c;
-            if (p.out_value) p.out_value[o] = c >= 0 ? rr_key_value((uint32_t)(best >> 32)) : -INFINITY;
+            if (p.out_value) p.out_value[o] = c >= 0 ? key_value((uint32_t)(best >> 32)) : -INFINITY;
         }
         if (c < 0 || t + 1 == k) continue;                   // nothing left to choose from: the tail is -1 / -1 / -inf
         if ((c & (kWave - 1)) == lane) open &= ~(1u << (c >> 6));
@@ -290,8 +251,6 @@ __global__ __launch_bounds__(kRrBlock) void k_list_diversity(const RrArgs p) {
     }
 }
 
-bool rr_aligned(const void *p, size_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
-
 template <typename K>
 int rr_launch(K staged, K global, const RrArgs &p, int n_staged, void *stream_) {
     const unsigned grid = (unsigned)p.n_rows;
@@ -325,8 +284,8 @@ int lgc_rerank_mmr(const float *items, int64_t item_stride, int64_t n_items, int
         n_items >= INT32_MAX || n_rows >= INT32_MAX)
         return LGC_E_RANGE;
     if (cand_stride < n_cand || rel_stride < n_cand) return LGC_E_INVAL;
-    if (!rr_aligned(items, 4) || !rr_aligned(scale, 4) || !rr_aligned(rel, 4) || !rr_aligned(out_value, 4) ||
-        !rr_aligned(out_pos, 4) || !rr_aligned(status, 4) || !rr_aligned(cand, 8) || !rr_aligned(out_index, 8))
+    if (!aligned_to(items, 4) || !aligned_to(scale, 4) || !aligned_to(rel, 4) || !aligned_to(out_value, 4) ||
+        !aligned_to(out_pos, 4) || !aligned_to(status, 4) || !aligned_to(cand, 8) || !aligned_to(out_index, 8))
         return LGC_E_ALIGN;
     if (n_rows == 0) return 0;
 
@@ -366,7 +325,7 @@ int lgc_list_diversity(const float *items, int64_t item_stride, int64_t n_items,
     for (int i = 0; i < n_cutoffs; ++i)
         if (cutoffs[i] < 1 || cutoffs[i] > k || (i > 0 && cutoffs[i] <= cutoffs[i - 1])) return LGC_E_RANGE;
     if (list_stride < k) return LGC_E_INVAL;
-    if (!rr_aligned(items, 4) || !rr_aligned(scale, 4) || !rr_aligned(status, 4) || !rr_aligned(lists, 8) || !rr_aligned(out, 8))
+    if (!aligned_to(items, 4) || !aligned_to(scale, 4) || !aligned_to(status, 4) || !aligned_to(lists, 8) || !aligned_to(out, 8))
         return LGC_E_ALIGN;
     if (n_rows == 0) return 0;
 

@@ -20,16 +20,6 @@ namespace {
 constexpr int kTopkMax = 256;
 constexpr int kTopkBlock = 1024;   // 16 wavefronts on one row: a single-row request is latency-bound on one CU
 
-// Ascending with the value.  Every NaN, whatever its sign bit and payload, takes the one top key: torch.topk ranks NaN
-// as the largest value, and the sign of the NaN a seen +-inf score turns into (inf * 0) is the hardware's choice.  Equal
-// keys are ordered by index, so NaNs come first by index, then +inf, the finite values (-0 = +0), then -inf.
-__device__ __forceinline__ uint32_t order_key(float v) {
-    const float w = __fadd_rn(v, 0.0f);                       // -0 -> +0: they compare equal (a seen item's 0 * score)
-    const uint32_t u = __float_as_uint(w);
-    const uint32_t key = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-    return w != w ? 0xFFFFFFFFu : key;
-}
-
 constexpr int kTopkRegs = 64;      // keys a thread can hold: rows up to kTopkRegs * kTopkBlock columns are read once
 constexpr int kTopkCopies = 4;     // histogram copies (lane & 3), one bank apart: scores crowd into a few exponent bins
 constexpr int kTopkHistStride = 2049;
@@ -309,17 +299,7 @@ __global__ __launch_bounds__(kTopkBlock) void k_mask_topk(const float *__restric
 // ----------------------------------------------------------------------------------------
 // Mini-batch sampler
 // ----------------------------------------------------------------------------------------
-// splitmix64 finaliser as a counter-based generator: draw(seed, step, sample, attempt) is stateless.
-__device__ __forceinline__ uint64_t mix64(uint64_t z) {
-    z += 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
-// unbiased integer in [0, range): 64-bit multiply-high of a 64-bit draw (bias < range / 2^64)
-__device__ __forceinline__ uint64_t bounded(uint64_t r, uint64_t range) { return __umul64hi(r, range); }
-
+// the stream is mix64 / bounded of lgconv_common.h, which lgc_sample_hard_triples draws from as well
 __global__ void k_sample_triples(const int64_t *__restrict__ users, int64_t n, const int32_t *__restrict__ pos_ptr,
                                  const int64_t *__restrict__ pos_items, const int32_t *__restrict__ ign_ptr,
                                  const int64_t *__restrict__ ign_items, int64_t n_users, int64_t n_items,
@@ -341,11 +321,7 @@ __global__ void k_sample_triples(const int64_t *__restrict__ users, int64_t n, c
     bool ok = false;
     for (int attempt = 0; attempt < 256 && !ok; ++attempt) {
         cand = n_users + (int64_t)bounded(mix64(key + 0x632BE59BD9B4E019ull * (uint64_t)(attempt + 1)), (uint64_t)n_items);
-        int32_t lo = ib, hi = ie;                       // binary search in the sorted ignore set
-        while (lo < hi) {
-            const int32_t mid = lo + ((hi - lo) >> 1);
-            if (ign_items[mid] < cand) lo = mid + 1; else hi = mid;
-        }
+        const int32_t lo = lower_bound(ign_items, ib, ie, cand);   // in_sorted, spelled out
         ok = !(lo < ie && ign_items[lo] == cand);
     }
     if (!ok) atomicOr(status, LGC_ST_SAMPLER_EXHAUSTED);
@@ -371,22 +347,6 @@ __host__ __device__ inline int score_b_stride(int dim) {
     return 4 * (g | 1);
 }
 
-// Four floats of a table row starting at column d; columns >= dim read as 0 and are never touched (the row may end
-// there: padding columns, the next row, or the end of the allocation).
-__device__ __forceinline__ f4 load_row4(const float *__restrict__ row, int d, int dim, bool live) {
-    f4 v = {0.0f, 0.0f, 0.0f, 0.0f};
-    if (live) {
-        if (d + 4 <= dim) {
-            v = *reinterpret_cast<const f4u *>(row + d);
-        } else {
-            if (d + 0 < dim) v.x = row[d + 0];
-            if (d + 1 < dim) v.y = row[d + 1];
-            if (d + 2 < dim) v.z = row[d + 2];
-        }
-    }
-    return v;
-}
-
 __global__ __launch_bounds__(kBlock) void k_score_rows(const float *__restrict__ users, int64_t user_stride,
                                                       int64_t n_user_rows, const int64_t *__restrict__ row_ids,
                                                       int64_t n_rows, const float *__restrict__ items,
@@ -405,7 +365,7 @@ __global__ __launch_bounds__(kBlock) void k_score_rows(const float *__restrict__
     for (int e = tid; e < kScoreBN * groups; e += kBlock) {
         const int it = e / groups, g = e - it * groups;
         const int64_t gi = min(item0 + it, n_items - 1);
-        *reinterpret_cast<f4 *>(Bs + it * bs + 4 * g) = load_row4(items + gi * item_stride, 4 * g, dim, true);
+        *reinterpret_cast<f4 *>(Bs + it * bs + 4 * g) = load4<false>(items + gi * item_stride, 4 * g, dim);
     }
 
     // staging of the user chunk: thread -> (row ar + 32 q, columns 4 ag ..) for q = 0, 1
@@ -433,7 +393,7 @@ __global__ __launch_bounds__(kBlock) void k_score_rows(const float *__restrict__
             for (int j = 0; j < 8; ++j) acc[i][j] = 0.0f;
         f4 stage[2];
 #pragma unroll
-        for (int q = 0; q < 2; ++q) stage[q] = load_row4(arow[q], 4 * ag, dim, alive[q] && 4 * ag < dim4);
+        for (int q = 0; q < 2; ++q) stage[q] = load4_if(arow[q], 4 * ag, dim, alive[q] && 4 * ag < dim4);
         for (int k0 = 0; k0 < dim4; k0 += kScoreKC) {
             __syncthreads();                                 // the previous chunk (and, first time, nothing) is consumed
 #pragma unroll
@@ -443,7 +403,7 @@ __global__ __launch_bounds__(kBlock) void k_score_rows(const float *__restrict__
             const int kn = k0 + kScoreKC;
             if (kn < dim4) {
 #pragma unroll
-                for (int q = 0; q < 2; ++q) stage[q] = load_row4(arow[q], kn + 4 * ag, dim, alive[q] && kn + 4 * ag < dim4);
+                for (int q = 0; q < 2; ++q) stage[q] = load4_if(arow[q], kn + 4 * ag, dim, alive[q] && kn + 4 * ag < dim4);
             }
             const int steps = min(kScoreKC, dim4 - k0) / 4;  // block-uniform
             for (int s = 0; s < steps; ++s) {
@@ -453,11 +413,9 @@ __global__ __launch_bounds__(kBlock) void k_score_rows(const float *__restrict__
 #pragma unroll
                 for (int j = 0; j < 8; ++j) b[j] = *reinterpret_cast<const f4 *>(Bs + (tx + 16 * j) * bs + k0 + 4 * s);
 #pragma unroll
-                for (int kk = 0; kk < 4; ++kk)
+                for (int i = 0; i < 4; ++i)
 #pragma unroll
-                    for (int i = 0; i < 4; ++i)
-#pragma unroll
-                        for (int j = 0; j < 8; ++j) acc[i][j] = __fmaf_rn(a[i][kk], b[j][kk], acc[i][j]);
+                    for (int j = 0; j < 8; ++j) acc[i][j] = score_chain(a[i], b[j], acc[i][j]);
             }
         }
 #pragma unroll
@@ -766,11 +724,10 @@ int lgc_mask_topk(const float *scores, int64_t score_stride, const float *seen, 
     static const topk_fn kerns[2][3] = {{k_mask_topk<false, 0>, k_mask_topk<false, 1>, k_mask_topk<false, 2>},
                                         {k_mask_topk<true, 0>, k_mask_topk<true, 1>, k_mask_topk<true, 2>}};
     const topk_fn kern = kerns[regs][mode];
-    if (lds > 16 * 1024) {    // static LDS (histogram copies, candidates) + the bitmask can pass the 64 KiB default
-        static unsigned long long lds_ok_topk[2][3] = {};
-        const int rc_attr = allow_big_lds(reinterpret_cast<const void *>(kern), 120 * 1024, &lds_ok_topk[regs][mode]);
-        if (rc_attr != 0) return rc_attr;
-    }
+    static unsigned long long lds_ok_topk[2][3] = {};
+    // above 16 KiB: static LDS (histogram copies, candidates) + the bitmask can pass the 64 KiB default
+    const int rc_attr = allow_lds(reinterpret_cast<const void *>(kern), lds, 16 * 1024, 120 * 1024, &lds_ok_topk[regs][mode]);
+    if (rc_attr != 0) return rc_attr;
     hipLaunchKernelGGL(kern, dim3((unsigned)n_rows), dim3(kTopkBlock), lds, as_stream(stream_), scores, score_stride, seen,
                        seen_stride, list_ptr, list_items, list_rows, n_cols, k, out_index, out_value);
     return (int)hipGetLastError();
@@ -797,11 +754,9 @@ int lgc_score_rows(const float *users, int64_t user_stride, int64_t n_user_rows,
     if (n_rows >= INT32_MAX || n_user_rows >= INT32_MAX) return LGC_E_RANGE;
     if (n_rows == 0) return 0;
     const size_t lds = (size_t)(kScoreBN * score_b_stride(dim) + kScoreBM * kScoreAStride) * 4 + kScoreBM * sizeof(int);
-    if (lds > 48 * 1024) {
-        static unsigned long long lds_ok_score = 0;
-        const int rc_attr = allow_big_lds(reinterpret_cast<const void *>(k_score_rows), 144 * 1024, &lds_ok_score);
-        if (rc_attr != 0) return rc_attr;
-    }
+    static unsigned long long lds_ok_score = 0;
+    const int rc_attr = allow_lds(reinterpret_cast<const void *>(k_score_rows), lds, 48 * 1024, 144 * 1024, &lds_ok_score);
+    if (rc_attr != 0) return rc_attr;
     // enough workgroups for every CU twice over: the row tiles of a panel are split only when the item tiles are few
     const int64_t item_tiles = ceil_div(n_items, kScoreBN), row_tiles = ceil_div(n_rows, kScoreBM);
     const int64_t split = std::min<int64_t>(row_tiles, std::max<int64_t>(1, 512 / item_tiles));

@@ -1,29 +1,15 @@
 // lgconv_similar.hip -- similar items: the k nearest rows of the item table by dot product or cosine, scored on the fp32
 // matrix cores and selected in the same launch; no score is ever written to memory.
 // C ABI: include/lgconv_hip.h
-#include "lgconv_common.h"
+#include "lgconv_tile.h"
 
 namespace {
 
-typedef unsigned long long u64;
-
-// Geometry.  A workgroup owns kNbBM query rows: gathered through query_ids and staged once in LDS,
-// whole width, zero-padded to 16 columns.  Its slice of the catalogue passes through LDS in tiles of kNbBN items, each in
-// chunks of kNbKC columns (the next chunk is already in registers while the current one is multiplied).  Wavefront w
-// scores all kNbBM rows against items [32 w, 32 w + 32) of the tile: 4 x 2 accumulators of v_mfma_f32_16x16x4_f32, all
-// independent.  Lane l holds A[row l & 15][k = l >> 4] and B[k = l >> 4][item l & 15]; one instruction adds k = 0, 1, 2, 3
-// in that order to the chain, so a 16-column group is four instructions and the chain runs over d ascending from +0 --
-// lgc_score_rows' chain.  Inside a group the LDS images hold column 4 j + q at position 4 q + j, so that the four
-// operands lane quarter q needs (steps j = 0 .. 3) are ONE 16-byte read.
-constexpr int kNbBM = 64, kNbBN = 128, kNbKC = 32;
-constexpr int kNbBS = kNbKC + 4;              // floats; (stride / 4) odd: 16 consecutive rows hit 16 different bank quads
-constexpr int kNbStage = kNbBN * (kNbKC / 4) / kBlock;   // float4 groups of a chunk a thread holds
+// Geometry: the tile of lgconv_tile.h.  A workgroup owns kTileBM query rows, gathered through
+// query_ids, and a slice of the catalogue's tiles; the epilogue of a tile selects.
 constexpr int kNbCapMax = 128;                // a candidate buffer is compacted by one wavefront, two entries a lane
-constexpr int kNbRowsPerWave = kNbBM / (kBlock / kWave);
-static_assert(kNbStage * kBlock == kNbBN * (kNbKC / 4), "a chunk is dealt evenly over the workgroup");
+constexpr int kNbRowsPerWave = kTileBM / (kBlock / kWave);
 static_assert(LGC_NEIGHBORS_MAX_K <= 64 && kNbCapMax == 2 * kWave, "compact_row holds a buffer in two registers a lane");
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 struct NbArgs {
     const float *items;
@@ -39,47 +25,10 @@ struct NbArgs {
     int32_t exclude_self, k, slices, cap, item_tiles;
 };
 
-// lgc_mask_topk's total order (lgconv_serve.hip): ascending with the value, every NaN the one top key, -0 = +0
-__device__ __forceinline__ uint32_t order_key(float v) {
-    const float w = __fadd_rn(v, 0.0f);
-    const uint32_t u = __float_as_uint(w);
-    const uint32_t key = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-    return w != w ? 0xFFFFFFFFu : key;
-}
-
-// the value a key stands for (the NaN key gives the positive quiet NaN 0x7FFFFFFF)
-__device__ __forceinline__ float key_value(uint32_t key) {
-    return __uint_as_float((key & 0x80000000u) ? (key & 0x7FFFFFFFu) : ~key);
-}
-
-// A candidate is ONE 64-bit word: the order key above the complemented item index, so that a larger word is a better
+// A candidate is ONE 64-bit word: the order key (order_key) above the complemented item index, so that a larger word is a better
 // candidate (greater value, or equal value and smaller index) and no two candidates of a row are equal.  0 = no candidate
 // (the smallest real key is -inf's 0x007FFFFF).
 __device__ __forceinline__ u64 pack_candidate(float v, int item) { return ((u64)order_key(v) << 32) | (uint32_t)~item; }
-
-// Four floats of a table row starting at column d; columns >= dim read as 0 and are never touched.
-__device__ __forceinline__ f4 nb_load4(const float *__restrict__ row, int d, int dim, bool live) {
-    f4 v = {0.0f, 0.0f, 0.0f, 0.0f};
-    if (live) {
-        if (d + 4 <= dim) {
-            v = *reinterpret_cast<const f4u *>(row + d);
-        } else {
-            if (d + 0 < dim) v.x = row[d + 0];
-            if (d + 1 < dim) v.y = row[d + 1];
-            if (d + 2 < dim) v.z = row[d + 2];
-        }
-    }
-    return v;
-}
-
-// columns c0 .. c0 + 3 (c0 % 4 == 0) of a row image whose 16-column groups are permuted as above
-__device__ __forceinline__ void nb_store4(float *row, int c0, f4 v) {
-    float *g = row + (c0 & ~15) + ((c0 & 15) >> 2);
-    g[0] = v.x;
-    g[4] = v.y;
-    g[8] = v.z;
-    g[12] = v.w;
-}
 
 // One wavefront sorts the n <= kNbCapMax candidates of buf in descending order and keeps the first k: every lane holds two
 // of them and counts how many are greater (they are all different), which is the place it writes its own to.  Reads and
@@ -122,19 +71,18 @@ __device__ __forceinline__ void nb_write_out(const NbArgs &p, int64_t o, u64 e) 
 
 __global__ __launch_bounds__(kBlock) void k_item_neighbors(const NbArgs p) {
     extern __shared__ __attribute__((aligned(16))) float nb_lds[];
-    const int sq = p.dp + 4, cap = p.cap, k = p.k, dim = p.dim;
-    float *Qs = nb_lds;                                      // [kNbBM][sq]: the query rows
-    float *Bs = Qs + kNbBM * sq;                             // [kNbBN][kNbBS]: a chunk of the item tile
-    u64 *buf = reinterpret_cast<u64 *>(Bs + kNbBN * kNbBS);  // [kNbBM][cap]: the candidates of a row
-    u64 *thr = buf + kNbBM * cap;                            // [kNbBM]: what a new candidate has to beat
-    int *cnt = reinterpret_cast<int *>(thr + kNbBM);         // [kNbBM]
-    int *qid = cnt + kNbBM;                                  // [kNbBM]: the item a row asks about, -1 = no row
-    float *qsc = reinterpret_cast<float *>(qid + kNbBM);     // [kNbBM]: scale[query]
-    float *thv = qsc + kNbBM;                                // [kNbBM]: the value of thr's key (-inf while there is none)
-    const int tid = threadIdx.x, lane = tid & (kWave - 1), w = tid >> 6, c = lane & 15, q = lane >> 4;
-    const int64_t row0 = (int64_t)blockIdx.x * kNbBM;
+    const int cap = p.cap, k = p.k, dim = p.dim;
+    Tile tl(nb_lds, p.dp);                                   // Qs: the query rows; Bs: a chunk of the item tile
+    u64 *buf = reinterpret_cast<u64 *>(tl.lds_end());        // [kTileBM][cap]: the candidates of a row
+    u64 *thr = buf + kTileBM * cap;                          // [kTileBM]: what a new candidate has to beat
+    int *cnt = reinterpret_cast<int *>(thr + kTileBM);       // [kTileBM]
+    int *qid = cnt + kTileBM;                                // [kTileBM]: the item a row asks about, -1 = no row
+    float *qsc = reinterpret_cast<float *>(qid + kTileBM);   // [kTileBM]: scale[query]
+    float *thv = qsc + kTileBM;                              // [kTileBM]: the value of thr's key (-inf while there is none)
+    const int tid = tl.tid, lane = tid & (kWave - 1), w = tl.w, c = tl.c, q = tl.q;
+    const int64_t row0 = (int64_t)blockIdx.x * kTileBM;
 
-    if (tid < kNbBM) {
+    if (tid < kTileBM) {
         const int64_t r = row0 + tid;
         int64_t id = -1;
         if (r < p.n_queries) {
@@ -151,39 +99,22 @@ __global__ __launch_bounds__(kBlock) void k_item_neighbors(const NbArgs p) {
         thv[tid] = -INFINITY;
     }
     __syncthreads();
-    const int qgroups = p.dp / 4;
-    for (int e = tid; e < kNbBM * qgroups; e += kBlock) {
-        const int row = e / qgroups, g = e - row * qgroups;
-        const int id = qid[row];
-        nb_store4(Qs + row * sq, 4 * g, nb_load4(p.items + (int64_t)max(id, 0) * p.item_stride, 4 * g, dim, id >= 0));
-    }
+    tl.stage_rows(p.items, p.item_stride, dim, [&](int row) { return qid[row]; });
 
     // this slice's item tiles, and the steps (tile, chunk) over them
     const int t_lo = (int)((int64_t)p.item_tiles * blockIdx.y / p.slices);
     const int t_hi = (int)((int64_t)p.item_tiles * (blockIdx.y + 1) / p.slices);
-    const int nch = (p.dp + kNbKC - 1) / kNbKC;
+    const int nch = (p.dp + kTileKC - 1) / kTileKC;
     const int n_steps = (t_hi - t_lo) * nch;
 
-    f4 stage[kNbStage];
     auto load_chunk = [&](int step) {
-        const int tile = t_lo + step / nch, ch = step % nch;
-#pragma unroll
-        for (int i = 0; i < kNbStage; ++i) {
-            const int e = tid + kBlock * i, it = e >> 3, g = e & 7;
-            const int item = tile * kNbBN + it, d = ch * kNbKC + 4 * g;
-            const bool live = (uint32_t)item < (uint32_t)p.n_items && d < dim;   // below 2^31 + 128: compared unsigned
-            stage[i] = nb_load4(p.items + (int64_t)(live ? item : 0) * p.item_stride, d, dim, live);
-        }
-    };
-    auto store_chunk = [&]() {
-#pragma unroll
-        for (int i = 0; i < kNbStage; ++i) {
-            const int e = tid + kBlock * i, it = e >> 3, g = e & 7;
-            nb_store4(Bs + it * kNbBS, 4 * g, stage[i]);
-        }
+        const int tile = t_lo + step / nch;
+        tl.load_chunk(p.items, p.item_stride, dim, step % nch, [&](int it) {
+            const uint32_t item = (uint32_t)tile * kTileBN + it;                   // below 2^31 + 128: unsigned, no overflow
+            return item < (uint32_t)p.n_items ? (int)item : -1;
+        });
     };
 
-    f32x4 acc[4][2];
     int item[2];
     bool iok[2];
     float isc[2];
@@ -191,40 +122,21 @@ __global__ __launch_bounds__(kBlock) void k_item_neighbors(const NbArgs p) {
     for (int step = 0; step < n_steps; ++step) {
         const int tile = t_lo + step / nch, ch = step % nch;
         if (ch == 0) {
-#pragma unroll
-            for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-                for (int nj = 0; nj < 2; ++nj) acc[mi][nj] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+            tl.reset();
             // what the epilogue needs of this lane's two items, requested a whole tile of products ahead
 #pragma unroll
             for (int nj = 0; nj < 2; ++nj) {
-                item[nj] = tile * kNbBN + 32 * w + 16 * nj + c;
+                item[nj] = tile * kTileBN + 32 * w + 16 * nj + c;
                 const bool inside = (uint32_t)item[nj] < (uint32_t)p.n_items;   // below 2^31 + 128: compared unsigned
                 iok[nj] = inside && (!p.item_ok || p.item_ok[item[nj]] != 0);
                 isc[nj] = (p.scale && inside) ? p.scale[item[nj]] : 1.0f;
             }
         }
         __syncthreads();                                     // the previous chunk is consumed
-        store_chunk();
+        tl.store_chunk();
         __syncthreads();                                     // also orders the query rows before their first use
         if (step + 1 < n_steps) load_chunk(step + 1);        // in flight during this chunk's products
-        const int groups = min(kNbKC / 16, p.dp / 16 - ch * (kNbKC / 16));
-        for (int g = 0; g < groups; ++g) {
-            f4 a[4], b[2];
-#pragma unroll
-            for (int mi = 0; mi < 4; ++mi)
-                a[mi] = *reinterpret_cast<const f4 *>(Qs + (16 * mi + c) * sq + ch * kNbKC + 16 * g + 4 * q);
-#pragma unroll
-            for (int nj = 0; nj < 2; ++nj)
-                b[nj] = *reinterpret_cast<const f4 *>(Bs + (32 * w + 16 * nj + c) * kNbBS + 16 * g + 4 * q);
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-#pragma unroll
-                for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-                    for (int nj = 0; nj < 2; ++nj)
-                        acc[mi][nj] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[mi][j], b[nj][j], acc[mi][nj], 0, 0, 0);
-        }
+        tl.product(ch);
         if (ch != nch - 1) continue;
 
         // The tile's scores are whole: lane (c, q) holds rows 16 mi + 4 q + r of items 32 w + 16 nj + c.  First the filter,
@@ -239,9 +151,9 @@ __global__ __launch_bounds__(kBlock) void k_item_neighbors(const NbArgs p) {
                 const float tv = thv[row], rs = qsc[row];
 #pragma unroll
                 for (int nj = 0; nj < 2; ++nj) {
-                    float s = acc[mi][nj][r];
+                    float s = tl.acc[mi][nj][r];
                     if (p.scale) s = __fmul_rn(__fmul_rn(s, rs), isc[nj]);
-                    acc[mi][nj][r] = s;
+                    tl.acc[mi][nj][r] = s;
                     todo |= (s < tv) ? 0u : 1u << ((mi * 4 + r) * 2 + nj);
                 }
             }
@@ -263,7 +175,7 @@ __global__ __launch_bounds__(kBlock) void k_item_neighbors(const NbArgs p) {
                         const int id = qid[row];
                         bool pending = false;
                         if (id >= 0 && iok[nj] && !(p.exclude_self && item[nj] == id)) {
-                            const u64 e = pack_candidate(acc[mi][nj][r], item[nj]);
+                            const u64 e = pack_candidate(tl.acc[mi][nj][r], item[nj]);
                             if (e > thr[row]) {
                                 const int pos = atomicAdd(&cnt[row], 1);
                                 if (pos < cap) buf[row * cap + pos] = e;
@@ -340,22 +252,10 @@ __global__ __launch_bounds__(kBlock) void k_row_rnorm(const float *__restrict__ 
     out[r] = v;
 }
 
-bool aligned_to(const void *p, size_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
-
 inline int nb_cap(int k) { return k <= 32 ? 64 : 96; }
 
-// The slice count in use: the one asked for, or with 0 the smallest that gives about 512 workgroups (two for every CU);
-// never more than there are item tiles.
-inline int nb_slices(int64_t n_queries, int64_t n_items, int slices) {
-    const int64_t item_tiles = (n_items + kNbBN - 1) / kNbBN, row_tiles = std::max<int64_t>(1, (n_queries + kNbBM - 1) / kNbBM);
-    int64_t s = slices > 0 ? slices : (512 + row_tiles - 1) / row_tiles;
-    s = std::min<int64_t>(s, 64);
-    return (int)std::max<int64_t>(1, std::min<int64_t>(s, item_tiles));
-}
-
 inline bool nb_sizes_ok(int64_t n_queries, int64_t n_items, int k, int slices) {
-    return n_queries >= 0 && n_items >= 1 && n_queries < INT32_MAX && n_items < INT32_MAX && k >= 1 &&
-           k <= LGC_NEIGHBORS_MAX_K && slices >= 0 && slices <= 64;
+    return tile_sizes_ok(n_queries, n_items, slices) && k >= 1 && k <= LGC_NEIGHBORS_MAX_K;
 }
 
 unsigned long long lds_ok_neighbors;
@@ -377,7 +277,7 @@ int lgc_row_rnorm(const float *table, int64_t stride, int64_t n_rows, int32_t di
 
 size_t lgc_item_neighbors_workspace_bytes(int64_t n_queries, int64_t n_items, int32_t k, int32_t slices) {
     if (!nb_sizes_ok(n_queries, n_items, k, slices)) return 0;
-    const int64_t item_tiles = (n_items + kNbBN - 1) / kNbBN;
+    const int64_t item_tiles = (n_items + kTileBN - 1) / kTileBN;
     int64_t places;                                          // candidate lists of k places
     if (slices > 0) {
         const int64_t s = std::min<int64_t>(slices, item_tiles);
@@ -385,7 +285,7 @@ size_t lgc_item_neighbors_workspace_bytes(int64_t n_queries, int64_t n_items, in
     } else {
         // what the chosen count needs is not monotonic in n_queries (more row tiles, fewer slices); its two bounds are
         const int64_t s_max = std::min<int64_t>(64, item_tiles);
-        places = s_max > 1 ? std::min<int64_t>(n_queries * s_max, n_queries + 512 * (int64_t)kNbBM) : 0;
+        places = s_max > 1 ? std::min<int64_t>(n_queries * s_max, n_queries + 512 * (int64_t)kTileBM) : 0;
     }
     return (size_t)places * (size_t)k * sizeof(u64);
 }
@@ -401,7 +301,7 @@ int lgc_item_neighbors(const float *items, int64_t item_stride, int64_t n_items,
     if (!aligned_to(items, 4) || !aligned_to(scale, 4) || !aligned_to(out_value, 4) || !aligned_to(out_index, 8) ||
         !aligned_to(workspace, 8))
         return LGC_E_ALIGN;
-    const int s = nb_slices(n_queries, n_items, slices);
+    const int s = tile_slices(n_queries, n_items, slices);
     const size_t need = s > 1 ? (size_t)n_queries * s * k * sizeof(u64) : 0;
     if (need > 0 && (!workspace || workspace_bytes < need)) return LGC_E_WORKSPACE;
     if (n_queries == 0) return 0;
@@ -419,21 +319,19 @@ int lgc_item_neighbors(const float *items, int64_t item_stride, int64_t n_items,
     p.n_items = (int32_t)n_items;
     p.n_queries = (int32_t)n_queries;
     p.dim = dim;
-    p.dp = (dim + 15) & ~15;
+    p.dp = tile_dp(dim);
     p.exclude_self = exclude_self;
     p.k = k;
     p.slices = s;
     p.cap = nb_cap(k);
-    p.item_tiles = (int32_t)((n_items + kNbBN - 1) / kNbBN);
-    const size_t lds = sizeof(float) * ((size_t)kNbBM * (p.dp + 4) + (size_t)kNbBN * kNbBS) +
-                       sizeof(u64) * ((size_t)kNbBM * p.cap + kNbBM) + (sizeof(int) * 2 + sizeof(float) * 2) * kNbBM;
-    if (lds > 48 * 1024) {
-        const int rc_attr = allow_big_lds(reinterpret_cast<const void *>(k_item_neighbors), 144 * 1024, &lds_ok_neighbors);
-        if (rc_attr != 0) return rc_attr;
-    }
-    const int64_t row_tiles = (n_queries + kNbBM - 1) / kNbBM;
+    p.item_tiles = (int32_t)((n_items + kTileBN - 1) / kTileBN);
+    const size_t lds = sizeof(float) * tile_lds_floats(p.dp) + sizeof(u64) * ((size_t)kTileBM * p.cap + kTileBM) +
+                       (sizeof(int) * 2 + sizeof(float) * 2) * kTileBM;
+    int rc = allow_lds(reinterpret_cast<const void *>(k_item_neighbors), lds, 48 * 1024, 144 * 1024, &lds_ok_neighbors);
+    if (rc != 0) return rc;
+    const int64_t row_tiles = (n_queries + kTileBM - 1) / kTileBM;
     hipLaunchKernelGGL(k_item_neighbors, dim3((unsigned)row_tiles, (unsigned)s), dim3(kBlock), lds, as_stream(stream_), p);
-    int rc = (int)hipGetLastError();
+    rc = (int)hipGetLastError();
     if (rc != 0 || s == 1) return rc;
     hipLaunchKernelGGL(k_neighbors_merge, dim3((unsigned)ceil_div(n_queries, kBlock / kWave)), dim3(kBlock), 0,
                        as_stream(stream_), p);

@@ -3,35 +3,27 @@
 // the sampler's ignore lists, and the loss, the gradient of the logits and the two gradient products with respect to the
 // propagated rows come out of five launches in stream order.  No float atomics: the same bits on every run.
 // C ABI: include/lgconv_hip.h
-#include "lgconv_common.h"
+#include "lgconv_tile.h"
 
 namespace {
 
 // Geometry.
-//   k_sm_logits   a workgroup owns kSmBM batch rows and ONE tile of kSmBN candidates, which passes through LDS in chunks of
-//                 kSmKC columns -- k_rank_sweep's tile (lgconv_fullrank.hip) and its operand layout: wavefront w scores all
-//                 rows against candidates [32 w, 32 w + 32) with 4 x 2 accumulators of v_mfma_f32_16x16x4_f32, one
-//                 instruction adds k = 0 .. 3 in order, so a score is lgc_score_rows' chain over d ascending from +0.  The
-//                 epilogue turns the score into the logit, decides admissibility (a binary search in the user's ignore
-//                 list) and writes the panel Z: the logit of an admissible pair (any NaN as the one quiet NaN), the word
-//                 kSmMark for every other pair.  There are no slices: a row's statistics are taken from Z by ONE wavefront.
+//   k_sm_logits   the tile of lgconv_tile.h: a workgroup owns kTileBM batch rows and ONE tile of kTileBN candidates, whose
+//                 table rows go through citem[].  The epilogue turns the score into the logit, decides admissibility (a
+//                 search in the user's ignore list) and writes the panel Z: the logit of an admissible pair (any NaN as
+//                 the one quiet NaN), the word kSmMark for every other pair.  There are no slices: a row's statistics are
+//                 taken from Z by ONE wavefront.
 //   k_sm_rows     one wavefront per batch row over its row of Z: maximum, sum of exponentials, loss, and G in place of Z.
 //   k_sm_loss     one workgroup: the row losses summed in a fixed order, divided by size.
 //   k_sm_product  out = G . E_c (grad_users) and out = G^T . E_u (grad_cands): a workgroup owns 16 output rows and 64
 //                 output columns, wavefront w columns [16 w, 16 w + 16); the inner extent passes through LDS in chunks of
 //                 kSmPK and ONE accumulator per output element takes it in ascending order.
-constexpr int kSmBM = 64, kSmBN = 128, kSmKC = 32;
-constexpr int kSmBS = kSmKC + 4;              // floats; (stride / 4) odd: 16 consecutive rows hit 16 different bank quads
-constexpr int kSmStage = kSmBN * (kSmKC / 4) / kBlock;   // float4 groups of a chunk a thread holds
 constexpr int kSmRows = kBlock / kWave;       // batch rows of a k_sm_rows workgroup
 constexpr int kSmPM = 16, kSmPN = 64, kSmPK = 64;        // k_sm_product: output rows, output columns, inner chunk
 constexpr int kSmPAS = kSmPK + 4;             // A rows: lane (c, q) reads c * 68 + q, 64 different banks
 constexpr int kSmPBS = kSmPN + 16;            // B rows: lane (c, q) reads q * 80 + c, 64 different banks
 constexpr uint32_t kSmMark = 0xFFFFFFFFu;     // Z: the pair is not admissible (a NaN bit pattern no admissible logit keeps)
 constexpr uint32_t kSmNan = 0x7FC00000u;      // Z: an admissible logit that is a NaN
-static_assert(kSmStage * kBlock == kSmBN * (kSmKC / 4), "a chunk is dealt evenly over the workgroup");
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 struct SmArgs {
     const float *table;
@@ -45,52 +37,26 @@ struct SmArgs {
     int32_t table_rows, split, n_rows, n_cand, dim, dp;   // dp = dim rounded up to 16
 };
 
-// Four floats of a table row starting at column d (d % 4 == 0); columns >= dim read as 0 and are never touched (the row
-// may end there: padding columns, the next row, or the end of the allocation).  Nothing is read where `live` is false.
-__device__ __forceinline__ f4 sm_load4_if(const float *__restrict__ row, int d, int dim, bool live) {
-    f4 v = {0.0f, 0.0f, 0.0f, 0.0f};
-    if (live) {
-        if (d + 4 <= dim) {
-            v = *reinterpret_cast<const f4u *>(row + d);
-        } else {
-            if (d + 0 < dim) v.x = row[d + 0];
-            if (d + 1 < dim) v.y = row[d + 1];
-            if (d + 2 < dim) v.z = row[d + 2];
-        }
-    }
-    return v;
-}
-
-// columns c0 .. c0 + 3 (c0 % 4 == 0) of a row image whose 16-column groups hold column 4 j + q at position 4 q + j
-__device__ __forceinline__ void sm_store4(float *row, int c0, f4 v) {
-    float *g = row + (c0 & ~15) + ((c0 & 15) >> 2);
-    g[0] = v.x;
-    g[4] = v.y;
-    g[8] = v.z;
-    g[12] = v.w;
-}
-
 // ----------------------------------------------------------------------------------------
 // the logits panel
 // ----------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kBlock) void k_sm_logits(const SmArgs p) {
     extern __shared__ __attribute__((aligned(16))) float sm_lds[];
-    const int sq = p.dp + 4, dim = p.dim;
-    float *Qs = sm_lds;                                      // [kSmBM][sq]: the user rows
-    float *Bs = Qs + kSmBM * sq;                             // [kSmBN][kSmBS]: a chunk of the candidate tile
-    float *cbias = Bs + kSmBN * kSmBS;                       // [kSmBN]: the bias of a column
-    int *citem = reinterpret_cast<int *>(cbias + kSmBN);     // [kSmBN]: the node of a column, -1 = none or not an item
-    int *uid = citem + kSmBN;                                // [kSmBM]: the user of a row, -1 = no valid row
-    int *tcol = uid + kSmBM;                                 // [kSmBM]: its target column, -1 = no valid row
-    int *titem = tcol + kSmBM;                               // [kSmBM]: the node of the target column
-    int *ibeg = titem + kSmBM;                               // [kSmBM]: the user's ignore list, [ibeg, iend)
-    int *iend = ibeg + kSmBM;
-    const int tid = threadIdx.x, lane = tid & (kWave - 1), w = tid >> 6, c = lane & 15, q = lane >> 4;
-    const int64_t row0 = (int64_t)blockIdx.x * kSmBM;
-    const uint32_t col0 = blockIdx.y * (uint32_t)kSmBN;      // below 2^31 + 128: unsigned, no overflow
+    const int dim = p.dim;
+    Tile tl(sm_lds, p.dp);                                   // Qs: the user rows; Bs: a chunk of the candidate tile
+    float *cbias = tl.lds_end();                             // [kTileBN]: the bias of a column
+    int *citem = reinterpret_cast<int *>(cbias + kTileBN);   // [kTileBN]: the node of a column, -1 = none or not an item
+    int *uid = citem + kTileBN;                              // [kTileBM]: the user of a row, -1 = no valid row
+    int *tcol = uid + kTileBM;                               // [kTileBM]: its target column, -1 = no valid row
+    int *titem = tcol + kTileBM;                             // [kTileBM]: the node of the target column
+    int *ibeg = titem + kTileBM;                             // [kTileBM]: the user's ignore list, [ibeg, iend)
+    int *iend = ibeg + kTileBM;
+    const int tid = tl.tid, w = tl.w, c = tl.c, q = tl.q;
+    const int64_t row0 = (int64_t)blockIdx.x * kTileBM;
+    const uint32_t col0 = blockIdx.y * (uint32_t)kTileBN;    // below 2^31 + 128: unsigned, no overflow
 
     // every id is range-checked here, before an address is formed from it
-    if (tid < kSmBM) {
+    if (tid < kTileBM) {
         const int64_t r = row0 + tid;
         int u = -1, t = -1, ti = -1, ib = 0, ie = 0;
         if (r < p.n_rows) {
@@ -118,7 +84,7 @@ __global__ __launch_bounds__(kBlock) void k_sm_logits(const SmArgs p) {
         ibeg[tid] = ib;
         iend[tid] = ie;
     }
-    if (tid < kSmBN) {
+    if (tid < kTileBN) {
         const uint32_t col = col0 + tid;
         int node = -1;
         float bias = 0.0f;
@@ -132,59 +98,35 @@ __global__ __launch_bounds__(kBlock) void k_sm_logits(const SmArgs p) {
         cbias[tid] = bias;
     }
     __syncthreads();
-    const int qgroups = p.dp / 4;
-    for (int e = tid; e < kSmBM * qgroups; e += kBlock) {
-        const int row = e / qgroups, g = e - row * qgroups;
-        const int u = uid[row];
-        sm_store4(Qs + row * sq, 4 * g, sm_load4_if(p.table + (int64_t)max(u, 0) * p.stride, 4 * g, dim, u >= 0 && 4 * g < dim));
-    }
+    tl.stage_rows(p.table, p.stride, dim, [&](int row) { return uid[row]; });
 
-    const int nch = (p.dp + kSmKC - 1) / kSmKC;
-    f4 stage[kSmStage];
-    auto load_chunk = [&](int ch) {
-#pragma unroll
-        for (int i = 0; i < kSmStage; ++i) {
-            const int e = tid + kBlock * i, it = e >> 3, g = e & 7;
-            const int node = citem[it];
-            const int d = ch * kSmKC + 4 * g;
-            stage[i] = sm_load4_if(p.table + (int64_t)max(node, 0) * p.stride, d, dim, node >= 0 && d < dim);
-        }
-    };
-    auto store_chunk = [&]() {
-#pragma unroll
-        for (int i = 0; i < kSmStage; ++i) {
-            const int e = tid + kBlock * i, it = e >> 3, g = e & 7;
-            sm_store4(Bs + it * kSmBS, 4 * g, stage[i]);
-        }
-    };
-
-    f32x4 acc[4][2];
-#pragma unroll
-    for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-        for (int nj = 0; nj < 2; ++nj) acc[mi][nj] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+    const int nch = (p.dp + kTileKC - 1) / kTileKC;
+    auto load_chunk = [&](int ch) { tl.load_chunk(p.table, p.stride, dim, ch, [&](int it) { return citem[it]; }); };
+    tl.reset();
     load_chunk(0);
     for (int ch = 0; ch < nch; ++ch) {
         __syncthreads();                                     // the previous chunk is consumed
-        store_chunk();
+        tl.store_chunk();
         __syncthreads();                                     // also orders the user rows before their first use
         if (ch + 1 < nch) load_chunk(ch + 1);                // in flight during this chunk's products
-        const int groups = min(kSmKC / 16, p.dp / 16 - ch * (kSmKC / 16));
+        // Tile::product (lgconv_tile.h), restated: as a call it costs this kernel 8 VGPRs and with them one of its five
+        // wavefronts per SIMD
+        const int groups = min(kTileKC / 16, p.dp / 16 - ch * (kTileKC / 16));
         for (int g = 0; g < groups; ++g) {
             f4 a[4], b[2];
 #pragma unroll
             for (int mi = 0; mi < 4; ++mi)
-                a[mi] = *reinterpret_cast<const f4 *>(Qs + (16 * mi + c) * sq + ch * kSmKC + 16 * g + 4 * q);
+                a[mi] = *reinterpret_cast<const f4 *>(tl.Qs + (16 * mi + c) * tl.sq + ch * kTileKC + 16 * g + 4 * q);
 #pragma unroll
             for (int nj = 0; nj < 2; ++nj)
-                b[nj] = *reinterpret_cast<const f4 *>(Bs + (32 * w + 16 * nj + c) * kSmBS + 16 * g + 4 * q);
+                b[nj] = *reinterpret_cast<const f4 *>(tl.Bs + (32 * w + 16 * nj + c) * kTileBS + 16 * g + 4 * q);
 #pragma unroll
             for (int j = 0; j < 4; ++j)
 #pragma unroll
                 for (int mi = 0; mi < 4; ++mi)
 #pragma unroll
                     for (int nj = 0; nj < 2; ++nj)
-                        acc[mi][nj] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[mi][j], b[nj][j], acc[mi][nj], 0, 0, 0);
+                        tl.acc[mi][nj] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[mi][j], b[nj][j], tl.acc[mi][nj], 0, 0, 0);
         }
     }
 
@@ -200,7 +142,7 @@ __global__ __launch_bounds__(kBlock) void k_sm_logits(const SmArgs p) {
             const int cl = 32 * w + 16 * nj + c;
             const uint32_t gc = col0 + cl;
             if (gc >= (uint32_t)p.n_cand) continue;
-            float z = __fmul_rn(acc[x >> 2][nj][x & 3], p.inv_tau);
+            float z = __fmul_rn(tl.acc[x >> 2][nj][x & 3], p.inv_tau);
             if (p.cand_bias) z = __fadd_rn(z, cbias[cl]);
             bool adm = false;
             if (t >= 0) {
@@ -208,12 +150,7 @@ __global__ __launch_bounds__(kBlock) void k_sm_logits(const SmArgs p) {
                 if ((int)gc == t) {
                     adm = true;
                 } else if (node >= 0 && node != ti) {
-                    int lo = ib, hi = ie;                    // binary search in the sorted ignore set; never leaves [ib, ie)
-                    while (lo < hi) {
-                        const int mid = lo + ((hi - lo) >> 1);
-                        if (p.ign_items[mid] < (int64_t)node) lo = mid + 1; else hi = mid;
-                    }
-                    adm = !(lo < ie && p.ign_items[lo] == (int64_t)node);
+                    adm = !in_sorted(p.ign_items, ib, ie, (int64_t)node);
                 }
             }
             const uint32_t bits = adm ? (z != z ? kSmNan : __float_as_uint(z)) : kSmMark;
@@ -225,7 +162,9 @@ __global__ __launch_bounds__(kBlock) void k_sm_logits(const SmArgs p) {
 // ----------------------------------------------------------------------------------------
 // a row of Z -> its loss and its row of G: wavefront = row, lane = column in rounds of 64
 // ----------------------------------------------------------------------------------------
-__device__ __forceinline__ float sm_wave_sum(float v) {     // a butterfly: the same order on every run, the sum in every lane
+// A float butterfly from distance 1 up, the sum in every lane: the order is part of the result (the tests restate it), so
+// this is not the shared wave_sum, which runs from distance 32 down.
+__device__ __forceinline__ float sm_wave_sum(float v) {
 #pragma unroll
     for (int m = 1; m < kWave; m <<= 1) v = __fadd_rn(v, __shfl_xor(v, m, kWave));
     return v;
@@ -374,11 +313,9 @@ __global__ __launch_bounds__(kBlock) void k_sm_product(const SmArgs p) {
     }
 }
 
-bool aligned_to(const void *p, size_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
-
 inline bool sm_sizes_ok(int64_t n_rows, int64_t n_cand) {
     if (n_rows < 0 || n_cand < 0 || n_rows > INT32_MAX || n_cand > INT32_MAX) return false;
-    return n_cand <= (int64_t)65535 * kSmBN;                 // candidate tiles are the grid's second extent; with it the
+    return n_cand <= (int64_t)65535 * kTileBN;                 // candidate tiles are the grid's second extent; with it the
                                                              // panel stays below 2^54 floats: its bytes fit 64 bits
 }
 
@@ -444,17 +381,14 @@ int lgc_softmax_batch(const float *table, int64_t stride, int64_t table_rows, in
     p.n_rows = (int32_t)n_rows;
     p.n_cand = (int32_t)n_cand;
     p.dim = dim;
-    p.dp = (dim + 15) & ~15;
+    p.dp = tile_dp(dim);
 
-    const size_t lds = sizeof(float) * ((size_t)kSmBM * (p.dp + 4) + (size_t)kSmBN * kSmBS + kSmBN) +
-                       sizeof(int) * (kSmBN + 5 * kSmBM);
-    if (lds > 48 * 1024) {
-        const int rc_attr = allow_big_lds(reinterpret_cast<const void *>(k_sm_logits), 96 * 1024, &lds_ok_sm_logits);
-        if (rc_attr != 0) return rc_attr;
-    }
-    const unsigned row_tiles = (unsigned)((n_rows + kSmBM - 1) / kSmBM), cand_tiles = (unsigned)((n_cand + kSmBN - 1) / kSmBN);
+    const size_t lds = sizeof(float) * (tile_lds_floats(p.dp) + kTileBN) + sizeof(int) * (kTileBN + 5 * kTileBM);
+    int rc = allow_lds(reinterpret_cast<const void *>(k_sm_logits), lds, 48 * 1024, 96 * 1024, &lds_ok_sm_logits);
+    if (rc != 0) return rc;
+    const unsigned row_tiles = (unsigned)((n_rows + kTileBM - 1) / kTileBM), cand_tiles = (unsigned)((n_cand + kTileBN - 1) / kTileBN);
     hipLaunchKernelGGL(k_sm_logits, dim3(row_tiles, cand_tiles), dim3(kBlock), lds, stream, p);
-    int rc = (int)hipGetLastError();
+    rc = (int)hipGetLastError();
     if (rc != 0) return rc;
     hipLaunchKernelGGL(k_sm_rows, dim3(ceil_div(n_rows, kSmRows)), dim3(kBlock), 0, stream, p);
     rc = (int)hipGetLastError();

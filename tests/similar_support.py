@@ -6,8 +6,8 @@ import numpy as np
 
 import topk_support as ts
 
-ROW_TILE = 64        # query rows of one workgroup (kNbBM)
-ITEM_TILE = 128      # items of one tile (kNbBN)
+ROW_TILE = 64        # query rows of one workgroup (kTileBM of csrc/lgconv_tile.h)
+ITEM_TILE = 128      # items of one tile (kTileBN)
 MAX_K = 64
 NEG_INF = np.float32(-np.inf)
 
