@@ -196,6 +196,12 @@ CASES = [
     case("r130_c1_d64", 130, 1, 64),
     case("r1_c260_d90_hits", 1, 260, 90, "dense", "hits", inv_tau=7.0),
     case("r63_c127_d61_misaligned_long_bias", 63, 127, 61, "misaligned", "long", bias=True),
+    # widths of one, two and three 16-column groups: one chunk, and two chunks whose second holds ONE group
+    case("r65_c129_d16_hits", 65, 129, 16, "dense", "hits", inv_tau=2.0),
+    case("r65_c129_d17_misaligned_long_bias", 65, 129, 17, "misaligned", "long", bias=True, inv_tau=3.0),
+    case("r65_c129_d33_padded_hits", 65, 129, 33, "padded", "hits", inv_tau=1.5),
+    case("r65_c129_d48_empty_bias", 65, 129, 48, "dense", "empty", bias=True),
+    case("r65_c129_d49_padded_hits", 65, 129, 49, "padded", "hits", inv_tau=6.0),
     case("spread_r65_c129_d64_hits", 65, 129, 64, "dense", "hits", inv_tau=400.0, kind="spread"),
     case("bad_ids_r65_c129_d64_hits", 65, 129, 64, "padded", "hits", kind="bad"),
     case("nonfinite_r65_c129_d64", 65, 129, 64, "dense", "empty", bias=True, kind="nonfinite"),
