@@ -538,8 +538,10 @@ __global__ __launch_bounds__(kBlock) void k_spmm_rows(SpmmArgs p, const int64_t 
 // position whose id lies outside the operator half has none); k_rows_chunks: a fixed grid of wavefronts strides over the
 // chunk numbers, finds the list position that owns a chunk (a 64-ary search: the lanes probe 64 offsets at once) and
 // either finishes the row (one chunk: rows of up to 32 entries in entry order, the bits of the tiled kernels) or leaves
-// a partial row; k_rows_combine adds the partial rows of a position in chunk order and applies the epilogue.  A repeated
-// id is computed once per occurrence and written with the same bits.
+// a partial row; k_rows_combine adds the partial rows of a position by lane group (combine_core: the position's j-th chunk
+// goes to lane group j % G, every group adds its chunks in order from +0, the G group sums are then added in group order --
+// chunk order only where G = 1, from 129 columns up; chunk_core orders the entries of a span the same way) and applies
+// the epilogue.  A repeated id is computed once per occurrence and written with the same bits.
 constexpr int kRowsPlanBlock = 1024;
 #ifndef LGC_ROWS_CHUNK            // (-DLGC_ROWS_CHUNK=128 builds the A/B variant of profiles/r04g)
 #define LGC_ROWS_CHUNK 256

@@ -225,7 +225,14 @@ int lgc_spmm_rows(const int32_t *rowptr, const lgc_entry *entries, int32_t row_b
  * length: 256 entries, or longer when `partial_rows` would not hold that many chunks -> first chunk number of every list
  * position), a fixed grid of wavefronts striding over the chunk numbers (rows of up to 32 entries finish in entry order
  * with the bits of lgc_spmm_tiles; longer single-chunk rows finish directly; the others leave partial rows), and one
- * wavefront per cut position adding its partial rows in chunk order: deterministic, no float atomics.
+ * wavefront per cut position adding its partial rows by lane group: deterministic, no float atomics.
+ *   order of the sums   G = 64 / lanes per row lane groups (lanes per row = ceil(dim / 4) from 4 columns up, else dim).
+ *                 A span of more than 32 entries -- a whole row of one chunk, or one chunk -- hands entry k to lane group
+ *                 (k - begin) % G; every group adds its entries in order from +0, the group sums are added as
+ *                 ((g0 + g1) + g2) + ...  The partial rows of a cut position are added the same way: its j-th chunk by lane
+ *                 group j % G, each group in order from +0, then the groups in order.  That is plain chunk order only
+ *                 where G = 1, from 129 columns up.  lgc_spmm_rows sums every longer row as ONE span, so the two agree bit
+ *                 for bit on rows of one chunk and differ in association on cut rows.
  *   y_rows        rows of y (compact: >= n_ids; else > every listed id of the operator half, i.e. >= row_end)
  *   compact       0: y[row_ids[m]] is written (as lgc_spmm_rows); 1: y[m] is written -- a [n_ids, dim] table in list order
  *                 (positions whose id lies outside [row_begin, row_end) are left untouched), e.g. the block a rank of a
