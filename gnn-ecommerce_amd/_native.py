@@ -213,6 +213,10 @@ SIGNATURES = {
     "lgc_softmax_batch": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int32, c_void_p, c_int64, c_void_p, c_int64, c_void_p,
                                   c_void_p, c_void_p, c_void_p, c_float, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
                                   c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "lgc_retrieve_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int32, c_int32]),
+    "lgc_retrieve_topk": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int32, c_void_p, c_int64, c_void_p,
+                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int32, c_int32,
+                                  c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
 }
 
 
@@ -281,6 +285,8 @@ COLUMN_SUMS_MAX = 64
 ATTR_MAX_TARGETS = 64  # LGC_ATTR_MAX_TARGETS: target columns of one lgc_attribute launch
 ATTR_MAX_TOP = 8       # LGC_ATTR_MAX_TOP
 NEIGHBORS_MAX_K = 64   # LGC_NEIGHBORS_MAX_K
+RETRIEVE_MAX_K = 64    # LGC_RETRIEVE_MAX_K
+RETRIEVE_MAX_SLICES = 1024   # LGC_RETRIEVE_MAX_SLICES
 RERANK_MAX_CAND = 256  # LGC_RERANK_MAX_CAND
 HARDNEG_MAX_CAND = 256 # LGC_HARDNEG_MAX_CAND
 RANK_SEEN_MODES = {"zero": 0, "remove": 1}   # LGC_RANK_SEEN_ZERO, LGC_RANK_SEEN_REMOVE

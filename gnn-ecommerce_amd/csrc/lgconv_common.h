@@ -5,8 +5,9 @@
 //           (order_key, key_value), the guarded row loads (load4, load4_if), the four-step group of lgc_score_rows' chain
 //           (score_chain), the sampler's stream (mix64, bounded), the search in a sorted list (lower_bound, in_sorted),
 //           the wavefront reductions (wave_sum, wave_max, wave_or)
-// The 64 x 128 x 32 fp32-MFMA tile of the scoring units is lgconv_tile.h.  A helper moves here when a SECOND unit needs
-// it, under an unprefixed name, and its copy in the first unit goes; a unit never restates one of these.
+// The 64 x 128 x 32 fp32-MFMA tile of the scoring units is lgconv_tile.h, the selection two of them share is
+// lgconv_select.h.  A helper moves here when a SECOND unit needs it, under an unprefixed name, and its copy in the first
+// unit goes; a unit never restates one of these.
 #pragma once
 #include <hip/hip_runtime.h>
 

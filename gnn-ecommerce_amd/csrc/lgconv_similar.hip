@@ -1,15 +1,15 @@
 // lgconv_similar.hip -- similar items: the k nearest rows of the item table by dot product or cosine, scored on the fp32
 // matrix cores and selected in the same launch; no score is ever written to memory.
 // C ABI: include/lgconv_hip.h
+#include "lgconv_select.h"
 #include "lgconv_tile.h"
 
 namespace {
 
 // Geometry: the tile of lgconv_tile.h.  A workgroup owns kTileBM query rows, gathered through
 // query_ids, and a slice of the catalogue's tiles; the epilogue of a tile selects.
-constexpr int kNbCapMax = 128;                // a candidate buffer is compacted by one wavefront, two entries a lane
 constexpr int kNbRowsPerWave = kTileBM / (kBlock / kWave);
-static_assert(LGC_NEIGHBORS_MAX_K <= 64 && kNbCapMax == 2 * kWave, "compact_row holds a buffer in two registers a lane");
+static_assert(LGC_NEIGHBORS_MAX_K <= kSelectMaxK, "compact_row holds a buffer in two registers a lane");
 
 struct NbArgs {
     const float *items;
@@ -24,50 +24,6 @@ struct NbArgs {
     int32_t n_items, n_queries, dim, dp;      // dp = dim rounded up to 16
     int32_t exclude_self, k, slices, cap, item_tiles;
 };
-
-// A candidate is ONE 64-bit word: the order key (order_key) above the complemented item index, so that a larger word is a better
-// candidate (greater value, or equal value and smaller index) and no two candidates of a row are equal.  0 = no candidate
-// (the smallest real key is -inf's 0x007FFFFF).
-__device__ __forceinline__ u64 pack_candidate(float v, int item) { return ((u64)order_key(v) << 32) | (uint32_t)~item; }
-
-// One wavefront sorts the n <= kNbCapMax candidates of buf in descending order and keeps the first k: every lane holds two
-// of them and counts how many are greater (they are all different), which is the place it writes its own to.  Reads and
-// writes of one wavefront reach LDS in program order and every write depends on all the reads, so it works in place.
-// Returns the new count; *thr (if given) becomes the k-th candidate once there are k, and *thv the value it stands for.
-__device__ __forceinline__ int compact_row(u64 *buf, int n, int k, int lane, u64 *thr, float *thv) {
-    const u64 e0 = lane < n ? buf[lane] : 0ull, e1 = lane + kWave < n ? buf[lane + kWave] : 0ull;
-    int r0 = 0, r1 = 0;
-    for (int t0 = 0; t0 < n; t0 += 8) {                      // eight reads in flight; the buffers are multiples of 8 long
-        u64 x[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) x[i] = buf[t0 + i];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const u64 v = t0 + i < n ? x[i] : 0ull;          // what lies past n is stale
-            r0 += v > e0 ? 1 : 0;
-            if (n > kWave) r1 += v > e1 ? 1 : 0;             // the same for every lane: a short buffer has no second entry
-        }
-    }
-    if (lane < n && r0 < k) buf[r0] = e0;
-    if (lane + kWave < n && r1 < k) buf[r1] = e1;
-    if (thr && n >= k) {
-        if (lane < n && r0 == k - 1) {
-            *thr = e0;
-            *thv = key_value((uint32_t)(e0 >> 32));
-        }
-        if (lane + kWave < n && r1 == k - 1) {
-            *thr = e1;
-            *thv = key_value((uint32_t)(e1 >> 32));
-        }
-    }
-    return min(n, k);
-}
-
-// place j of a finished row: candidate e (0 = none)
-__device__ __forceinline__ void nb_write_out(const NbArgs &p, int64_t o, u64 e) {
-    p.out_index[o] = e ? (int64_t)(~(uint32_t)e & 0x7FFFFFFFu) : -1;
-    if (p.out_value) p.out_value[o] = e ? key_value((uint32_t)(e >> 32)) : -INFINITY;
-}
 
 __global__ __launch_bounds__(kBlock) void k_item_neighbors(const NbArgs p) {
     extern __shared__ __attribute__((aligned(16))) float nb_lds[];
@@ -208,32 +164,19 @@ __global__ __launch_bounds__(kBlock) void k_item_neighbors(const NbArgs p) {
         const int m = compact_row(buf + row * cap, min(cnt[row], cap), k, lane, nullptr, nullptr);
         if (lane < k) {
             const u64 e = lane < m ? buf[row * cap + lane] : 0ull;
-            if (p.slices == 1) nb_write_out(p, r * k + lane, e);
+            if (p.slices == 1) write_candidate(p.out_index, p.out_value, r * k + lane, e);
             else p.ws[(r * p.slices + blockIdx.y) * k + lane] = e;
         }
     }
 }
 
-// One wavefront per query row merges the slices' candidates: 64 at a time are appended to the row's buffer (empty places
-// skipped), which is compacted to the k best whenever another 64 might not fit.
+// One wavefront per query row merges the slices' candidates (merge_row).
 __global__ __launch_bounds__(kBlock) void k_neighbors_merge(const NbArgs p) {
     __shared__ u64 mbuf[kBlock / kWave][kNbCapMax];
     const int lane = threadIdx.x & (kWave - 1), w = threadIdx.x >> 6, k = p.k;
     const int64_t r = (int64_t)blockIdx.x * (kBlock / kWave) + w;
     if (r >= p.n_queries) return;
-    u64 *buf = mbuf[w];
-    const u64 *src = p.ws + r * p.slices * k;
-    const int total = p.slices * k;
-    int n = 0;
-    for (int base = 0; base < total; base += kWave) {
-        const u64 e = base + lane < total ? src[base + lane] : 0ull;
-        const u64 have = __ballot(e != 0ull);
-        if (e != 0ull) buf[n + __popcll(have & ((1ull << lane) - 1ull))] = e;
-        n += __popcll(have);
-        if (n > kNbCapMax - kWave) n = compact_row(buf, n, k, lane, nullptr, nullptr);
-    }
-    n = compact_row(buf, n, k, lane, nullptr, nullptr);
-    if (lane < k) nb_write_out(p, r * k + lane, lane < n ? buf[lane] : 0ull);
+    merge_row(mbuf[w], p.ws + r * p.slices * k, p.slices * k, k, lane, p.out_index, p.out_value, r * k);
 }
 
 // ss = one chain of fused multiply-adds over d ascending from +0; out = 1 / sqrt(ss), both correctly rounded, inf -> 0
@@ -251,8 +194,6 @@ __global__ __launch_bounds__(kBlock) void k_row_rnorm(const float *__restrict__ 
     if (v == INFINITY) v = 0.0f;
     out[r] = v;
 }
-
-inline int nb_cap(int k) { return k <= 32 ? 64 : 96; }
 
 inline bool nb_sizes_ok(int64_t n_queries, int64_t n_items, int k, int slices) {
     return tile_sizes_ok(n_queries, n_items, slices) && k >= 1 && k <= LGC_NEIGHBORS_MAX_K;
@@ -323,7 +264,7 @@ int lgc_item_neighbors(const float *items, int64_t item_stride, int64_t n_items,
     p.exclude_self = exclude_self;
     p.k = k;
     p.slices = s;
-    p.cap = nb_cap(k);
+    p.cap = select_cap(k);
     p.item_tiles = (int32_t)((n_items + kTileBN - 1) / kTileBN);
     const size_t lds = sizeof(float) * tile_lds_floats(p.dp) + sizeof(u64) * ((size_t)kTileBM * p.cap + kTileBM) +
                        (sizeof(int) * 2 + sizeof(float) * 2) * kTileBM;

@@ -1,5 +1,5 @@
 // lgconv_tile.h -- the 64 x 128 x 32 fp32-MFMA tile of the scoring units (lgconv_similar.hip, lgconv_fullrank.hip,
-// lgconv_softmax.hip; DESIGN.md sections 12a and 19).  The prologue (which ids index which table), the loop over tiles and
+// lgconv_softmax.hip, lgconv_retrieve.hip; DESIGN.md sections 12a and 19).  The prologue (which ids index which table), the loop over tiles and
 // slices and the tile's epilogue are the unit's own; what they share is here, one definition each (Tile::product is the one
 // piece two of the kernels restate, for the registers a call costs them).
 //

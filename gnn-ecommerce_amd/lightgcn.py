@@ -14,7 +14,8 @@ distances and shortest paths from users to their recommended items (src/inferenc
 interaction lists (``foldin``); ``explain_topk`` and ``explain_sessions`` split every recommended item's score over the user's
 own items (``explain``); ``similar_items`` answers "which items are like this one?" (``similar``); ``recommend_diverse``,
 ``rerank_diverse`` and ``list_diversity`` re-rank a candidate list by greedy maximal marginal relevance and measure the
-intra-list diversity of the result (``rerank``).  What changes is underneath: propagation is the HIP CSR-SpMM with
+intra-list diversity of the result (``rerank``); ``recommend_filtered``, ``item_audience`` and ``similar_users`` retrieve across
+two tables with a catalogue filter and per-request exclusion lists that REMOVE what they list (``retrieve``).  What changes is underneath: propagation is the HIP CSR-SpMM with
 the layer sum fused (``propagate.propagate_sum``) and pair scoring is one gather-dot kernel.
 """
 from __future__ import annotations
@@ -33,7 +34,8 @@ from .foldin import SessionLists, fold_in, fold_table
 from .graph import get_graph
 from .lgconv import LGConv
 from .paths import shortest_paths
-from .similar import item_neighbors
+from .similar import METRICS, item_neighbors, row_rnorm
+from .retrieve import BuyerLists, request_lists, retrieve_topk
 from .fullrank import evaluate_full_rank
 from .propagate import (DEFAULT_WORKSPACE_BYTES, TOPK_MAX, PositiveLists, RegHook, SeenLists, bpr_loss_fused, column_sums,
                         evaluate_ranking, evaluate_topk, mask_topk, pair_dot, propagate_sum, recommend_topk,
@@ -416,6 +418,107 @@ class LightGCN(torch.nn.Module):
         if item_ok is not None:
             item_ok = torch.as_tensor(item_ok).to(device=item_t.device).contiguous()
         return item_neighbors(item_t, k, ids, metric, item_ok, True, 0)
+
+    # -- filtered retrieval across two tables ------------------------------------------------------
+    def _retrieve_tables(self, edge_index, edge_weight, n_users, n_items, k):
+        """(user rows, item rows) of the cached serving embedding, after the checks the three methods below share."""
+        n_users, n_items = int(n_users), int(n_items)
+        if n_users < 1 or n_items < 1 or n_users + n_items != self.num_nodes:
+            raise ValueError(f"n_users {n_users} + n_items {n_items} != {self.num_nodes} nodes")
+        if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= _native.RETRIEVE_MAX_K:
+            raise ValueError(f"k must be an integer in [1, {_native.RETRIEVE_MAX_K}]")
+        _native.require_device(self.embedding.weight, "LightGCN.embedding.weight")
+        with torch.no_grad():                                # read-only: the table recommendK keeps between requests
+            return torch.split(self._serving_embedding(edge_index, edge_weight).detach(), [n_users, n_items])
+
+    @staticmethod
+    def _ok_mask(ok, n: int, name: str):
+        if ok is None:
+            return None
+        ok = torch.as_tensor(ok)
+        if ok.dtype not in (torch.bool, torch.uint8) or ok.dim() != 1 or ok.numel() != n:
+            raise TypeError(f"{name} must be a bool or uint8 tensor of {n} entries")
+        return ok
+
+    @staticmethod
+    def _id_tensor(ids, name: str) -> Tensor:
+        t = ids if torch.is_tensor(ids) else torch.as_tensor(list(ids), dtype=torch.int64)
+        if t.dtype != torch.int64:
+            raise TypeError(f"{name} must be int64 indices")
+        return t.reshape(-1)
+
+    def recommend_filtered(self, edge_index, edge_weight, n_users, n_items, seen, users, k: int = 20, item_ok=None,
+                           exclude=None, queries: Optional[Tensor] = None):
+        """``(index int64 [n, k], value fp32 [n, k])`` on the device: per user of ``users`` the k best items that are in
+        stock and new to the user.  ``seen``: a ``SeenLists`` (or None) whose items are REMOVED -- they never compete,
+        unlike in ``recommend_topk``, where a seen item keeps upstream's score 0.  ``item_ok``: bool or uint8
+        ``[n_items]``, an item whose entry is 0 is returned to nobody.  ``exclude``: per request row a list of further item
+        indices (what is in the cart) or None, merged into the row's list.  With fewer than k eligible items a row ends in
+        -1 / -inf.  Session form: ``queries`` = the folded rows of ``embed_sessions`` (fp32 ``[n, D]``), ``users`` None and
+        ``seen`` = ``SessionLists.mask()``, whose list r belongs to row r.  See ``retrieve.retrieve_topk``."""
+        if seen is not None and not isinstance(seen, SeenLists):
+            raise TypeError("seen must be a SeenLists or None (SeenLists.from_dense converts the dense mask)")
+        item_ok = self._ok_mask(item_ok, int(n_items), "item_ok")
+        if (queries is None) == (users is None):
+            raise ValueError("give users (trained rows) or queries (folded rows), not both")
+        ids = None if users is None else self._id_tensor(users, "users")
+        user_t, item_t = self._retrieve_tables(edge_index, edge_weight, n_users, n_items, k)
+        dev = item_t.device
+        if queries is not None:
+            if not torch.is_tensor(queries) or queries.dim() != 2 or queries.size(1) != item_t.size(1):
+                raise TypeError(f"queries must be fp32 [n, {item_t.size(1)}] rows")
+            table, n = queries.to(device=dev, dtype=torch.float32), queries.size(0)
+        else:
+            ids = ids.to(dev).contiguous()
+            table, n = user_t, ids.numel()
+        if item_ok is not None:
+            item_ok = item_ok.to(dev).contiguous()
+        lists = list_rows = None
+        if exclude is not None or (queries is not None and seen is not None):
+            # the row's own ascending list: the union with `exclude`; a session's list comes in the visitor's order
+            lists = request_lists(seen, ids, n, exclude, int(n_items), dev)
+            list_rows = torch.arange(n, dtype=torch.int64, device=dev)
+        elif seen is not None:
+            lists = (seen.ptr.to(dev), seen.items.to(dev))    # list = the user's id
+        return retrieve_topk(table, item_t, k, ids, cand_ok=item_ok, lists=lists, list_rows=list_rows)
+
+    def item_audience(self, edge_index, edge_weight, n_users, n_items, item_ids, k: int = 20, buyers=None, user_ok=None):
+        """``(index int64 [n, k], value fp32 [n, k])`` on the device: per item of ``item_ids`` (item indices WITHOUT the
+        ``n_users`` offset) the k users whose rows score it best -- the audience of a product.  ``buyers``: a
+        ``BuyerLists`` whose users are removed from their items' answers; None builds it from ``edge_index`` (an int64
+        ``[2, E]`` tensor; anything else needs ``buyers``).  ``user_ok``: bool or uint8 ``[n_users]``, a user whose entry is
+        0 (opted out) is returned for nothing.  One pass over the user table; see ``retrieve.retrieve_topk``."""
+        user_ok = self._ok_mask(user_ok, int(n_users), "user_ok")
+        ids = self._id_tensor(item_ids, "item_ids")
+        if buyers is not None and not isinstance(buyers, BuyerLists):
+            raise TypeError("buyers must be a BuyerLists or None")
+        user_t, item_t = self._retrieve_tables(edge_index, edge_weight, n_users, n_items, k)
+        dev = user_t.device
+        if buyers is None:
+            if not (torch.is_tensor(edge_index) and edge_index.dim() == 2):
+                raise ValueError("buyers=None needs edge_index as an int64 [2, E] tensor (BuyerLists.from_edges)")
+            buyers = BuyerLists.from_edges(edge_index, int(n_users), int(n_items), dev)
+        if user_ok is not None:
+            user_ok = user_ok.to(dev).contiguous()
+        return retrieve_topk(item_t, user_t, k, ids.to(dev).contiguous(), cand_ok=user_ok,
+                             lists=(buyers.ptr.to(dev), buyers.items.to(dev)))
+
+    def similar_users(self, edge_index, edge_weight, n_users, n_items, user_ids, k: int = 10, metric: str = "cosine",
+                      user_ok=None):
+        """``(index int64 [n, k], value fp32 [n, k])`` on the device: per user of ``user_ids`` the k most similar OTHER
+        users by ``metric`` ("cosine" or "dot") over the user rows of the serving embedding -- lookalike users.
+        ``user_ok`` as in ``item_audience``.  The order and the tail of a short row are ``similar_items``'."""
+        if metric not in METRICS:
+            raise ValueError(f"metric must be one of {METRICS}, got {metric!r}")
+        user_ok = self._ok_mask(user_ok, int(n_users), "user_ok")
+        ids = self._id_tensor(user_ids, "user_ids")
+        user_t, _ = self._retrieve_tables(edge_index, edge_weight, n_users, n_items, k)
+        dev = user_t.device
+        ids = ids.to(dev).contiguous()
+        scale = row_rnorm(user_t) if metric == "cosine" else None
+        if user_ok is not None:
+            user_ok = user_ok.to(dev).contiguous()
+        return retrieve_topk(user_t, user_t, k, ids, scale, scale, user_ok, skip_id=ids)
 
     # -- k recommendations that are not k variants of one product ---------------------------------
     def _item_table(self, edge_index, edge_weight, n_users, n_items) -> Tensor:

@@ -25,7 +25,16 @@ returns what upstream returns, ``[{'items': [[k item indices], ...]}]``.  What d
     (``requests`` = what the body is otherwise, ``0 <= lam <= 1``, ``k <= N <= 256``, default ``min(5 k, 256, n_items)``) is
     answered with ``{"items": [[...]]}`` in request order: per request element its N best items re-ranked by greedy
     maximal marginal relevance, so that the k returned are relevant AND unlike each other (``LightGCN.recommend_diverse`` /
-    ``rerank_diverse``).  ``lam = 1`` is the plain answer.  It does not combine with ``"explain"``.
+    ``rerank_diverse``).  ``lam = 1`` is the plain answer.  It does not combine with ``"explain"``;
+  * a body ``{"requests": [...], "filter": {"allow": [item ids]} | {"deny": [item ids]}, "k": int (optional, 1 .. 64)}`` is
+    answered with ``{"items": [[...]]}`` in request order: per request element the k best items that pass the catalogue
+    filter, with the user's purchased items (a visitor's own purchased items) REMOVED instead of zeroed.  Next to what
+    ``requests`` otherwise holds an element may carry ``"exclude": [item ids]`` (what is in the cart), and ``{"user": id,
+    "exclude": [...]}`` without ``"items"`` is a trained user with exclusions.  Places that no item fills are dropped.  It
+    does not combine with ``"explain"`` or ``"diversify"`` (``LightGCN.recommend_filtered``);
+  * a body ``{"audience": [item ids], "k": int (optional, 1 .. 64, default 20), "deny_users": [user ids] (optional)}`` asks
+    about ITEMS' audiences: it is answered with ``{"users": [[...]], "scores": [[...]]}``, per item the users who score it
+    best, its buyers and the denied users left out (``LightGCN.item_audience``).
 """
 from __future__ import annotations
 
@@ -39,6 +48,7 @@ from .foldin import SessionLists
 from .graph import PropGraph
 from .lightgcn import LightGCN
 from .propagate import SeenLists
+from .retrieve import BuyerLists
 from .rerank import check_lam
 from .similar import METRICS
 
@@ -181,6 +191,118 @@ class RecommendHandler:
         return {"items": [[row[j] for j in js] for row, js in zip(index, keep)],
                 "scores": [[row[j] for j in js] for row, js in zip(value, keep)]}
 
+    @staticmethod
+    def _id_list(ids, what: str):
+        if not isinstance(ids, (list, tuple)) or any(isinstance(i, bool) or not isinstance(i, int) for i in ids):
+            raise ValueError(f"request body: {what} must be a list of indices")
+        return list(ids)
+
+    def _parse_k(self, body):
+        k = body.get("k", self.k)
+        if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= _native.RETRIEVE_MAX_K:
+            raise ValueError(f"request body: 'k' must be an integer in [1, {_native.RETRIEVE_MAX_K}]")
+        return k
+
+    def parse_filtered(self, body):
+        """``(requests, excludes, item_ok, k)`` of a body ``{"requests": [...], "filter": {...}, "k": optional}``:
+        ``requests`` without the ``"exclude"`` keys (``{"user": id, "exclude": [...]}`` becomes the plain id), ``excludes``
+        one list or None per element, ``item_ok`` a host uint8 ``[n_items]`` tensor or None.  A malformed body raises
+        ValueError, an id outside its table IndexError."""
+        for other in ("explain", "diversify"):
+            if other in body:
+                raise ValueError(f"request body: 'filter' and '{other}' do not combine")
+        unknown = set(body) - {"requests", "filter", "k"}
+        if unknown or "requests" not in body or "filter" not in body:
+            raise ValueError(f"request body: expected 'requests', 'filter' and optionally 'k'; got {sorted(map(str, body))}")
+        requests, flt, k = body["requests"], body["filter"], self._parse_k(body)
+        if not isinstance(requests, (list, tuple)):
+            raise ValueError("request body: 'requests' must be a list of user ids and / or dicts")
+        if not isinstance(flt, dict) or set(flt) - {"allow", "deny"} or len(flt) > 1:
+            raise ValueError("request body: 'filter' must be {'allow': [ids]} or {'deny': [ids]}")
+        item_ok = None
+        for name, ids in flt.items():
+            ids = self._id_list(ids, f"'filter.{name}'")
+            if any(i < 0 or i >= self.n_items for i in ids):
+                raise IndexError(f"item index outside [0, {self.n_items})")
+            item_ok = torch.full((self.n_items,), 1 if name == "deny" else 0, dtype=torch.uint8)
+            item_ok[torch.tensor(ids, dtype=torch.int64)] = 0 if name == "deny" else 1
+        plain, excludes = [], []
+        for pos, el in enumerate(requests):
+            extra = None
+            if isinstance(el, dict) and "exclude" in el:
+                extra = self._id_list(el["exclude"], f"element {pos}: 'exclude'")
+                if any(i < 0 or i >= self.n_items for i in extra):
+                    raise IndexError(f"item index outside [0, {self.n_items})")
+                el = {key: v for key, v in el.items() if key != "exclude"}
+                if set(el) == {"user"}:                      # a trained user with exclusions
+                    el = el["user"]
+            if isinstance(el, bool) or not isinstance(el, (int, dict)):
+                raise ValueError(f"request element {pos}: expected a user id or a dict, got {type(el).__name__}")
+            if isinstance(el, int) and (el < 0 or el >= self.n_users):
+                raise IndexError(f"user index outside [0, {self.n_users})")
+            plain.append(el)
+            excludes.append(extra)
+        return plain, excludes, item_ok, k
+
+    def inference_filtered(self, data, excludes, item_ok, k: int):
+        """Per request element the ``k`` best items that pass ``item_ok``, the purchased items and the element's
+        ``exclude`` removed: trained users and interaction lists through ``recommend_filtered``, in request order."""
+        id_pos, ids, session_pos, lists, init_users = self.parse_sessions(data)
+        answers = [None] * len(data)
+        if item_ok is not None:
+            item_ok = item_ok.to(self.device)
+
+        def keep(index, positions):
+            for pos, row in zip(positions, index.cpu().tolist()):
+                answers[pos] = [i for i in row if i >= 0]
+        with torch.no_grad():
+            if ids:
+                extra = [excludes[pos] for pos in id_pos]
+                index, _ = self.model.recommend_filtered(self.graph, None, self.n_users, self.n_items, self.seen, ids, k, item_ok,
+                                                         extra if any(e is not None for e in extra) else None)
+                keep(index, id_pos)
+            if lists:
+                sessions = SessionLists.from_lists(lists, self.device).validate(self.n_items, "request")
+                rows = self.model.embed_sessions(self.graph, None, self.n_users, self.n_items, sessions,
+                                                 init_users if any(u >= 0 for u in init_users) else None)
+                index, _ = self.model.recommend_filtered(self.graph, None, self.n_users, self.n_items, sessions.mask("purchased"),
+                                                         None, k, item_ok, [excludes[pos] for pos in session_pos], queries=rows)
+                keep(index, session_pos)
+        return {"items": answers}
+
+    def parse_audience(self, body):
+        """``(item ids, k, user_ok)`` of a body ``{"audience": [...], "k": optional, "deny_users": optional}``; ``user_ok`` a
+        host uint8 ``[n_users]`` tensor or None.  A malformed body raises ValueError, an id outside its table IndexError."""
+        unknown = set(body) - {"audience", "k", "deny_users"}
+        if unknown or "audience" not in body:
+            raise ValueError(f"request body: expected 'audience' and optionally 'k', 'deny_users'; got {sorted(map(str, body))}")
+        ids, k = self._id_list(body["audience"], "'audience'"), self._parse_k(body)
+        user_ok = None
+        if "deny_users" in body:
+            deny = self._id_list(body["deny_users"], "'deny_users'")
+            if any(u < 0 or u >= self.n_users for u in deny):
+                raise IndexError(f"user index outside [0, {self.n_users})")
+            user_ok = torch.ones(self.n_users, dtype=torch.uint8)
+            user_ok[torch.tensor(deny, dtype=torch.int64)] = 0
+        if any(i < 0 or i >= self.n_items for i in ids):
+            raise IndexError(f"item index outside [0, {self.n_items})")
+        return ids, k, user_ok
+
+    def inference_audience(self, ids, k: int, user_ok):
+        """Per asked-about item the ``k`` users who score it best and their scores, best first, without the users who
+        bought it (the transpose of the purchase lists, built once) and without the denied users; empty places dropped."""
+        if not ids:
+            return {"users": [], "scores": []}
+        if getattr(self, "buyers", None) is None:
+            self.buyers = BuyerLists.from_seen(self.seen, self.n_users, self.n_items)
+        with torch.no_grad():
+            index, value = self.model.item_audience(self.graph, None, self.n_users, self.n_items, ids, k, self.buyers,
+                                                    None if user_ok is None else user_ok.to(self.device))
+        index, value = index.cpu().tolist(), value.cpu().tolist()
+        keep = [[j for j, i in enumerate(row) if i >= 0] for row in index]
+        return {"users": [[row[j] for j in js] for row, js in zip(index, keep)],
+                "scores": [[row[j] for j in js] for row, js in zip(value, keep)]}
+
     def parse_diversify(self, body):
         """``(requests, lam, candidates, metric)`` of a body ``{"requests": [...], "diversify": lam, "candidates": optional,
         "metric": optional}``.  A malformed body raises ValueError, a user id outside ``[0, n_users)`` IndexError."""
@@ -270,6 +392,10 @@ class RecommendHandler:
         if isinstance(data, dict):
             if "similar" in data:
                 return self.inference_similar(*self.parse_similar(data))
+            if "audience" in data:
+                return self.inference_audience(*self.parse_audience(data))
+            if "filter" in data:
+                return self.inference_filtered(*self.parse_filtered(data))
             if "diversify" in data:
                 return self.inference_diverse(*self.parse_diversify(data))
             return self.inference_explained(*self.parse_explain(data))

@@ -1235,6 +1235,74 @@ int lgc_softmax_batch(const float *table, int64_t stride, int64_t table_rows, in
                       float *grad_users, float *grad_cands, int64_t grad_stride,
                       void *workspace, size_t workspace_bytes, int32_t *status, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Cross-table retrieval (an addition to ABI 14: exports only): per query row of ONE table the k best rows of ANOTHER, with
+ * a global eligibility mask, a per-query exclusion list and one skipped id per query -- "recommend, but never what is out of
+ * stock and never what this user already bought" (user -> items), "which users should hear about this product" (item ->
+ * users, its buyers left out) and lookalike users (user -> users).  Upstream's rule masked = score * (1 - seen) lets a seen
+ * item compete with score 0; here it is REMOVED.  Scoring runs on the fp32 matrix cores and the selection in the same
+ * launch, as in lgc_item_neighbors: no score is written to memory.
+ *
+ * lgc_retrieve_topk: per query the k best eligible candidates.
+ *   queries    fp32 [n_query_rows, dim], rows query_stride floats apart; cands fp32 [n_cand, dim], rows cand_stride floats
+ *              apart, n_cand >= 1.  Strides >= dim; columns at or past dim are never read.  The two tables may be the same
+ *              memory
+ *   query_ids  int64 [n_queries] rows of `queries`, any order, repeats allowed; NULL = query r is row r.  An id outside
+ *              [0, n_query_rows) sets LGC_ST_INDEX_OOB in `status` and its whole result row is -1 / -inf; every id is
+ *              range-checked before any address is formed from it
+ *   query_scale, cand_scale  fp32 [n_query_rows] and [n_cand], both or neither (LGC_E_INVAL otherwise): s = (dot *
+ *              query_scale[id]) * cand_scale[c], left to right, each product rounded, as in lgc_item_neighbors; without
+ *              them s = dot
+ *   cand_ok    uint8 [n_cand] or NULL: a candidate with cand_ok[c] == 0 is eligible for nobody
+ *   list_ptr, list_items  the exclusion lists, a CSR: int64 [n_lists + 1] and int64 entries, candidate indices.  list_ptr
+ *              is read on trust, as lgc_mask_topk and lgc_rank_positions read theirs.  list_ptr NULL = no lists (list_items
+ *              and list_rows are then ignored).  A list is ascending (ingest.seen_csr, SeenLists.from_dense); an entry
+ *              equal to its predecessor is harmless, an entry outside [0, n_cand) is ignored, an unsorted list gives an
+ *              unspecified selection but never an access out of range.  A candidate in the query's list is REMOVED; there is
+ *              no ZERO mode here (lgc_mask_topk and recommend_topk keep upstream's rule)
+ *   list_rows  int64 [n_queries] or NULL: the list of query r is number list_rows[r], with NULL it is the query's id.  -1 =
+ *              no list; any other value outside [0, n_lists) sets LGC_ST_INDEX_OOB and gives the row -1 / -inf -- a request
+ *              whose filter cannot be found is not answered unfiltered
+ *   skip_id    int64 [n_queries] or NULL: candidate skip_id[r] is not eligible for query r (the query's own row where both
+ *              tables are one); -1 or any value outside the table skips nothing
+ *   k          1 .. LGC_RETRIEVE_MAX_K
+ *   slices     0 .. LGC_RETRIEVE_MAX_SLICES: the candidate table is cut into that many ranges of 128-row tiles, one workgroup
+ *              per (64 queries, range), and a merge launch follows where there is more than one range; 0 = the library
+ *              chooses (the smallest count that gives about 512 workgroups); a count above the number of candidate tiles is
+ *              clamped to it.  The limit is not lgc_item_neighbors' 64: an audience request is one tile of queries over
+ *              thousands of candidate tiles.  The result does not depend on it
+ *   out_index  int64 [n_queries, k]; out_value fp32 [n_queries, k] or NULL.  With fewer than k eligible candidates the tail
+ *              of the row is -1 / -inf
+ *   workspace  device memory of at least lgc_retrieve_workspace_bytes(n_queries, n_cand, k, slices) bytes, 8-byte aligned:
+ *              n_queries * (ranges in use) * k words of 8 bytes where there is more than one range; may be NULL where that is
+ *              0.  The size function returns 0 for sizes the call would refuse and grows monotonically in n_queries, n_cand,
+ *              k and in slices over 1 .. LGC_RETRIEVE_MAX_SLICES
+ * Arithmetic: dot is lgc_score_rows' chain with the query row the first factor -- fused multiply-adds over d ascending from
+ * +0, zeros past dim -- so it has that function's bits, except that a sum of -0 may come out as +0.
+ * Order: lgc_mask_topk's total order -- every NaN first, then +inf, the finite values descending with -0 = +0, then -inf;
+ * equal elements by ascending index.  It is strict, so the result depends neither on the tile shape nor on `slices` nor on
+ * the order of arrival.  A NaN comes back as the quiet NaN 0x7FFFFFFF and -0 as +0.  No float atomics: the same bytes on
+ * every run.
+ * Errors before any launch, no output touched: LGC_E_DIM (as lgc_dim_ok); LGC_E_INVAL (a null required pointer -- queries,
+ * cands, out_index, status --, a negative count, a stride below dim, one scale without the other, list_ptr without
+ * list_items); LGC_E_RANGE (k or slices outside their ranges, n_cand < 1, n_queries, n_query_rows, n_cand or n_lists >=
+ * 2^31 - 1); LGC_E_ALIGN (an fp32 pointer not dword aligned, an int64 pointer or the workspace not 8-byte aligned);
+ * LGC_E_WORKSPACE (a workspace that is too small or missing).  n_queries == 0 validates, launches nothing and returns 0.
+ * ------------------------------------------------------------------------------------- */
+#define LGC_RETRIEVE_MAX_K 64
+#define LGC_RETRIEVE_MAX_SLICES 1024
+size_t lgc_retrieve_workspace_bytes(int64_t n_queries, int64_t n_cand, int32_t k, int32_t slices);
+int lgc_retrieve_topk(const float *queries, int64_t query_stride, int64_t n_query_rows,
+                      const float *cands, int64_t cand_stride, int64_t n_cand, int32_t dim,
+                      const int64_t *query_ids, int64_t n_queries,
+                      const float *query_scale, const float *cand_scale,
+                      const uint8_t *cand_ok,
+                      const int64_t *list_ptr, const int64_t *list_items, const int64_t *list_rows, int64_t n_lists,
+                      const int64_t *skip_id,
+                      int32_t k, int32_t slices,
+                      int64_t *out_index, float *out_value,
+                      void *workspace, size_t workspace_bytes, int32_t *status, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
