@@ -90,8 +90,28 @@ def graph_item_extremes():
     return (*_coo(240, pairs), 240, 290, 3)
 
 
+def graph_nothing_left():
+    """(g) 60 x 10, every user has at most 3 entries and no item row holds an entry (all of them dropped); T = 3: n_h = 0
+    and G_L is empty -- the item step of a reduced layer has no operator at all and only zeroes / copies the block."""
+    rng = np.random.default_rng(8)
+    pairs = [(59, 0)] + _lists(rng, 59, 10, lambda u: 1 + u % 3)
+    return (*_coo(60, pairs, drop_item_rows=range(len(pairs))), 60, 70, 3)
+
+
+def graph_kept_but_unnamed():
+    """(h) 80 x 12, even users have 1 .. 3 entries, odd users 4 .. 6 and no item row names them (their item-row entries
+    are dropped); T = 3: kept users exist, the item part of the reduced CSR is empty, G_L is not."""
+    rng = np.random.default_rng(9)
+    pairs = [(0, 0)] + _lists(rng, 80, 12, lambda u: (4 + u % 3) if u % 2 else ((u // 2) % 3 + (u > 0)))
+    return (*_coo(80, pairs, drop_item_rows=[k for k, p in enumerate(pairs) if p[0] % 2]), 80, 92, 3)
+
+
 GRAPHS = {"degrees_1_to_12": graph_degrees_1_to_12, "hub": graph_hub, "all_eliminated": graph_all_eliminated,
-          "none_eliminated": graph_none_eliminated, "directed": graph_directed, "item_extremes": graph_item_extremes}
+          "none_eliminated": graph_none_eliminated, "directed": graph_directed, "item_extremes": graph_item_extremes,
+          "nothing_left": graph_nothing_left, "kept_but_unnamed": graph_kept_but_unnamed}
+# built without normalisation: a row without entries has degree zero, and the normalised values on it would be zeros --
+# the point of these two is the path taken, with nonzero values
+UNNORMALISED = ("nothing_left", "kept_but_unnamed")
 
 
 def graph_sweep():

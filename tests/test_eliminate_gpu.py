@@ -11,7 +11,8 @@ import pytest
 import torch
 
 from conftest import ROOT, rel_fro, worst_row_rel
-from eliminate_support import (GRAPHS, alphas_for, csr_host, dense_fp64, eliminated_users, layer_sum_fp64, ulp32)
+from eliminate_support import (GRAPHS, UNNORMALISED, alphas_for, csr_host, dense_fp64, eliminated_users, layer_sum_fp64, ulp32)
+from reduce_support import reduce_reference_fast
 from gnn_ecommerce_amd import _native, graph as G, propagate, synth
 from gnn_ecommerce_amd.graph import PropGraph, build_reduced_csr
 
@@ -26,7 +27,7 @@ def built(name, device):
     """(PropGraph, split, n, T) of a named graph, built once per session; tests set ``eliminate_max_deg`` themselves."""
     if name not in _graphs:
         ei, ew, split, n, t = GRAPHS[name]()
-        pg = PropGraph(ei.to(device), ew.to(device), n)
+        pg = PropGraph(ei.to(device), ew.to(device), n, normalize=name not in UNNORMALISED)
         assert pg.split == split
         _graphs[name] = (pg, split, n, t)
     return _graphs[name]
@@ -109,6 +110,18 @@ def test_reduced_csr_and_gram_operator(device, name):
     assert (err <= ulp32(want)).all(), float((err / ulp32(want).clamp_min(1e-300)).max())
     if name == "hub":
         assert int(g_rowptr[n_h + 1] - g_rowptr[n_h]) > 256, "the hub's row must take several chunks"
+    if name == "nothing_left":
+        assert n_h == 0 and red.nnz == 0 and red.gram_nnz == 0 and op.nnz > 0
+    if name == "kept_but_unnamed":
+        assert n_h > 0 and red.nnz == red.user_nnz > 0 and red.gram_nnz > 0
+
+    # every output bit for bit against the exact host reference: G_L's values are the fp64 sums in expansion order
+    ref = reduce_reference_fast(op.rowptr.cpu().numpy(), op.entries[:, 0].cpu().numpy(), op.entries[:, 1].cpu().numpy(),
+                                split, n, t)
+    assert ref.pairs_min == ref.pairs_max == red.n_pairs and (ref.n_kept, ref.user_nnz) == (red.n_h, red.user_nnz)
+    for f, want_f in (("user_map", ref.user_map), ("rowptr", ref.rowptr), ("entries", ref.entries),
+                      ("gram_rowptr", ref.gram_rowptr), ("gram_entries", ref.gram_entries)):
+        assert torch.equal(getattr(red, f).cpu(), torch.from_numpy(want_f)), f"{f} differs from the host reference"
 
 
 def test_builder_argument_errors_come_before_any_launch():
