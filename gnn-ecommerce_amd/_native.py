@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import ctypes
 import os
+import threading
 from ctypes import CFUNCTYPE, POINTER, Structure, c_char_p, c_float, c_int, c_int32, c_int64, c_size_t, c_uint64, c_void_p
 from typing import Optional
 
@@ -265,6 +266,18 @@ def ptr(t: Optional[torch.Tensor]) -> Optional[int]:
 
 def stream_of(device: torch.device) -> int:
     return torch.cuda.current_stream(device).cuda_stream
+
+
+def scratch_owner(device: torch.device, stream: Optional[int] = None) -> tuple:
+    """(device, stream handle, host thread id): the one owner of a scratch buffer that lives across launches -- the partial
+    rows one launch of a hop writes and a later one reads, the flags a backward sets, pulls through and clears, a score
+    panel between its scoring and its ranking launch.  Work on such a buffer is ordered on ITS stream and issued by ITS
+    thread only, so two streams, or two threads on one stream (every thread's default), never share one.  ``stream``: the
+    handle the launches will get, when the caller has it already (None: the device's current stream is looked up; 0 for
+    a CPU device).  A stream that is being captured is an owner like any other."""
+    if stream is None:
+        stream = stream_of(device) if device.type == "cuda" else 0
+    return (device, stream, threading.get_ident())
 
 
 def require_device(t: torch.Tensor, name: str) -> None:

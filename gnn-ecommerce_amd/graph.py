@@ -450,15 +450,18 @@ class SweepPlan:
         m = arrays["multi"]
         wide = (m[:, 2] - m[:, 1]) > self.WIDE_SLOTS
         self.multi, self.multi_wide = m[~wide].contiguous().to(dev), m[wide].contiguous().to(dev)
-        self._partials: Dict[int, Tensor] = {}
+        self._partials: Dict[tuple, Tensor] = {}
 
     WIDE_SLOTS = 32
 
-    def partials(self, dim: int) -> Tensor:
-        buf = self._partials.get(dim)
+    def partials(self, dim: int, owner: Optional[tuple] = None) -> Tensor:
+        """The sweep's partial rows for tables of this width, one buffer per owner (``_native.scratch_owner``; None: the
+        calling thread on its current stream): lgc_sweep writes them and lgc_sweep_combine reads them in a later launch."""
+        key = (owner or _native.scratch_owner(self.slabs.device), dim)
+        buf = self._partials.get(key)
         if buf is None:
             buf = torch.empty((max(self.dims["n_slots"], 1), dim), dtype=torch.float32, device=self.slabs.device)
-            self._partials[dim] = buf
+            self._partials[key] = buf
         return buf
 
     def nbytes(self) -> int:
@@ -483,8 +486,8 @@ class Operator:
     sweep_light_len_wide: int = 0                   # ... and of its two-entry plan (68..96 columns)
     _sweep: Dict[int, SweepPlan] = field(default_factory=dict)     # by entries per step: 4 (61..64 columns), 2 (68..96)
     _tiles: Optional[List[TileClass]] = None
-    _partials: Dict[int, Tensor] = field(default_factory=dict)
-    _c_structs: Dict[tuple, list] = field(default_factory=dict)
+    _partials: Dict[tuple, Tensor] = field(default_factory=dict)       # by (owner, width): _native.scratch_owner
+    _c_structs: Dict[tuple, list] = field(default_factory=dict)        # by (owner, width, sweep)
     _row_stats: Optional[tuple] = None
 
     @classmethod
@@ -573,14 +576,20 @@ class Operator:
             self._row_stats = row_stats(self.rowptr, p.row_begin, p.row_end)
         return listed_rows_pay(self._row_stats, n_ids)
 
-    def partials(self, dim: int) -> Optional[Tensor]:
+    def partials(self, dim: int, owner: Optional[tuple] = None) -> Optional[Tensor]:
+        """The chunk plan's partial rows for tables of this width, one buffer per owner (``_native.scratch_owner``; None:
+        the calling thread on its current stream).  One launch of a hop writes them and a later one reads them, and
+        ``get_graph`` hands one operator to every caller in the process: two streams or two threads that run the same
+        operator at the same width must not meet in one buffer.  A buffer stays referenced for the operator's lifetime,
+        so a captured graph that holds its address stays valid."""
         n_slots = self.plan.n_slots
         if n_slots == 0:
             return None
-        buf = self._partials.get(dim)
+        key = (owner or _native.scratch_owner(self.rowptr.device), dim)
+        buf = self._partials.get(key)
         if buf is None:
             buf = torch.empty((n_slots, dim), dtype=torch.float32, device=self.rowptr.device)
-            self._partials[dim] = buf
+            self._partials[key] = buf
         return buf
 
     def values(self) -> Tensor:
@@ -589,11 +598,14 @@ class Operator:
     def columns(self) -> Tensor:
         return self.entries[:, 0]
 
-    def c_struct(self, dim: int, sweep: int) -> "_native.OperatorC":
+    def c_struct(self, dim: int, sweep: int, owner: Optional[tuple] = None) -> "_native.OperatorC":
         """The operator as the C ABI's ``lgc_operator`` (device pointers of tensors this object keeps alive), cached per
-        embedding width because the scratch buffers are per width."""
+        owner and embedding width because the scratch buffers are per owner and width (``owner``: ``_native.scratch_owner``
+        of the stream the struct will be launched on; None: the calling thread on its current stream)."""
         import ctypes
-        key = (dim, sweep)
+        if owner is None:
+            owner = _native.scratch_owner(self.rowptr.device)
+        key = (owner, dim, sweep)
         got = self._c_structs.get(key)
         if got is not None:
             return got[0]
@@ -602,7 +614,7 @@ class Operator:
         c.rowptr, c.entries = _native.ptr(self.rowptr), _native.ptr(self.entries)
         c.chunks = _native.ptr(p.chunks) if p.n_chunks else None
         c.multi = _native.ptr(p.multi) if p.n_multi else None
-        c.partials = _native.ptr(self.partials(dim))
+        c.partials = _native.ptr(self.partials(dim, owner))
         c.row_begin, c.row_end, c.short_max, c.n_chunks, c.n_multi = p.row_begin, p.row_end, p.short_max, p.n_chunks, p.n_multi
         c.tiles_per_wave = TILES_PER_WAVE
         keep = [c]
@@ -616,7 +628,7 @@ class Operator:
             sc = _native.SweepArraysC(_native.ptr(sw.slabs), _native.ptr(sw.wave_slab_ptr), _native.ptr(sw.wave_npieces),
                                       _native.ptr(sw.piece_slot), _native.ptr(sw.multi) if sw.multi.size(0) else None,
                                       _native.ptr(sw.multi_wide) if sw.multi_wide.size(0) else None,
-                                      _native.ptr(sw.partials(dim)), sw.dims["n_waves"], sw.dims["row_cap"], sw.multi.size(0),
+                                      _native.ptr(sw.partials(dim, owner)), sw.dims["n_waves"], sw.dims["row_cap"], sw.multi.size(0),
                                       sw.multi_wide.size(0), sw.dims["groups"])
             c.sweep = ctypes.pointer(sc)
             keep.append(sc)
@@ -638,13 +650,15 @@ class Operator:
             raise _native.NativeLibraryError(f"embedding width {dim} is not supported by the HIP kernels")
         table_rows = min(x.size(0), out.size(0))
         sweep = sweep_choice(lib, dim, table_rows, x.stride(0)) if self.sweep_cols is not None else 0
-        return lib, self.c_struct(dim, sweep), dim, table_rows
+        # the stream is read ONCE per hop: the same handle names the scratch's owner and receives the launches
+        stream = _native.stream_of(x.device)
+        return lib, self.c_struct(dim, sweep, _native.scratch_owner(x.device, stream)), dim, table_rows, stream
 
     def route(self, x: Tensor, out: Tensor, r: Optional[Tensor] = None) -> str:
         """The kernels ``apply(x, out, r=r)`` would launch, as ``lgc_apply_route`` names them: "fused_dpp", "sweep_wide",
         ... with "+wt" while the output rows leave through write-through stores.  Launches nothing."""
         import ctypes
-        lib, c, dim, table_rows = self._apply_args(x, out, r)
+        lib, c, dim, table_rows, _ = self._apply_args(x, out, r)
         code = lib.lgc_apply_route(ctypes.byref(c), table_rows, x.stride(0), out.stride(0), 0 if r is None else r.stride(0), dim)
         _native.check(min(code, 0), "lgc_apply_route")
         return _native.route_name(code)
@@ -660,7 +674,7 @@ class Operator:
         With ``r2`` (needs ``r``, and an operator that ``takes_second_row``):  (b2 * r2[row] + b * r[row]) + a * (A x)[row],
         the bits of ``_native.lincomb(out, [(b2, r2), (b, r), (a, A x)])`` -- one ``lgc_apply2``."""
         import ctypes
-        lib, c, dim, table_rows = self._apply_args(x, out, r)
+        lib, c, dim, table_rows, stream = self._apply_args(x, out, r)
         if r2 is not None:
             if r is None:
                 raise ValueError("r2 needs r")
@@ -670,13 +684,12 @@ class Operator:
             with torch.cuda.device(x.device):
                 code = lib.lgc_apply2(ctypes.byref(c), table_rows, _native.ptr(x), x.stride(0), _native.ptr(out), out.stride(0),
                                       _native.ptr(r), r.stride(0), _native.ptr(r2), r2.stride(0), float(a), float(b), float(b2),
-                                      dim, _native.stream_of(x.device))
+                                      dim, stream)
             _native.check(code, "lgc_apply2")
             return out
         with torch.cuda.device(x.device):
             code = lib.lgc_apply(ctypes.byref(c), table_rows, _native.ptr(x), x.stride(0), _native.ptr(out), out.stride(0),
-                                 _native.ptr(r), 0 if r is None else r.stride(0), float(a), float(b), dim,
-                                 _native.stream_of(x.device))
+                                 _native.ptr(r), 0 if r is None else r.stride(0), float(a), float(b), dim, stream)
         _native.check(code, "lgc_apply")
         return out
 
@@ -706,11 +719,11 @@ def listed_rows_pay(stats: Tuple[float, float, int], n_ids: int) -> bool:
 ROWS_SPLIT_ROOM = 16384      # partial rows beyond one per list position: 256-entry chunks up to 4 M listed entries
 
 
-def _rows_split_scratch(device: torch.device, n_ids: int, dim: int) -> Tuple[Tensor, Tensor]:
+def _rows_split_scratch(device: torch.device, n_ids: int, dim: int, stream: Optional[int] = None) -> Tuple[Tensor, Tensor]:
     """Scratch of lgc_spmm_rows_split (chunk numbers, partial rows), owned by one (device, stream, host thread) triple like
-    every other scratch buffer that lives across launches: two steps on different streams never share it."""
-    import threading
-    key = (device, torch.cuda.current_stream(device).cuda_stream, threading.get_ident(), dim)
+    every other scratch buffer that lives across launches: two steps on different streams never share it.  ``stream``:
+    the handle the launch will get (None: the current stream is looked up)."""
+    key = _native.scratch_owner(device, stream) + (dim,)
     got = _rows_scratch.get(key)
     if got is None or got[0].numel() < n_ids + 2:
         cap = max(n_ids, 4096)
@@ -754,12 +767,12 @@ def apply_rows(op: "Operator", rows: Tensor, x: Tensor, out: Tensor, a: float = 
                 return out
             if out.size(0) < (n_ids if compact else p.row_end):
                 raise ValueError("out has too few rows")
-            work, partials = _rows_split_scratch(x.device, n_ids, dim)
+            stream = _native.stream_of(x.device)
+            work, partials = _rows_split_scratch(x.device, n_ids, dim, stream)
             code = lib.lgc_spmm_rows_split(_native.ptr(op.rowptr), entries, p.row_begin, p.row_end, _native.ptr(rows),
                                            n_ids, x.size(0), _native.ptr(x), x.stride(0), _native.ptr(out), out.stride(0),
                                            out.size(0), _native.ptr(r), 0 if r is None else r.stride(0), float(a), float(b), dim,
-                                           int(compact), _native.ptr(work), _native.ptr(partials), partials.size(0),
-                                           _native.stream_of(x.device))
+                                           int(compact), _native.ptr(work), _native.ptr(partials), partials.size(0), stream)
             _native.check(code, "lgc_spmm_rows_split")
             return out
         code = lib.lgc_spmm_rows(_native.ptr(op.rowptr), entries, p.row_begin, p.row_end, _native.ptr(rows),

@@ -453,13 +453,14 @@ def _seed_pull(op: Operator, flag: Tensor, slot: Tensor, seed_vals: Tensor, out:
     as zeros without being read."""
     lib = _native.load()
     p = op.plan
+    stream = _native.stream_of(out.device)          # read once: the partial rows' owner and the launches' stream
+    partials = op.partials(out.size(1), _native.scratch_owner(out.device, stream))
     with torch.cuda.device(out.device):
         code = lib.lgc_seed_pull(_native.ptr(op.rowptr), _native.ptr(op.entries), p.row_begin, p.row_end, p.short_max,
                                  _native.ptr(p.chunks) if p.n_chunks else None, p.n_chunks,
-                                 _native.ptr(p.multi) if p.n_multi else None, p.n_multi, _native.ptr(op.partials(out.size(1))),
+                                 _native.ptr(p.multi) if p.n_multi else None, p.n_multi, _native.ptr(partials),
                                  _native.ptr(flag), _native.ptr(slot), _native.ptr(mark), _native.ptr(seed_vals),
-                                 seed_vals.stride(0), out.size(0), _native.ptr(out), out.stride(0), out.size(1),
-                                 _native.stream_of(out.device))
+                                 seed_vals.stride(0), out.size(0), _native.ptr(out), out.stride(0), out.size(1), stream)
     _native.check(code, "lgc_seed_pull")
 
 
@@ -480,9 +481,9 @@ def _scratch_key(device: torch.device):
     """Scratch that must be all zero between uses is owned by one (device, stream, host thread) triple: the set / pull /
     clear sequence of a backward pass is ordered on ITS stream and issued by ITS thread only, so two backward passes on
     different streams or threads (two models, a DataParallel-style host loop, the thread-ranks of
-    tests/test_partition_gpu.py) each get their own buffers instead of reading or clearing each other's flags."""
-    import threading
-    return (device, torch.cuda.current_stream(device).cuda_stream if device.type == "cuda" else 0, threading.get_ident())
+    tests/test_partition_gpu.py) each get their own buffers instead of reading or clearing each other's flags.
+    ``_native.scratch_owner``: the same key owns the hop's partial rows (graph.py) and the score panel."""
+    return _native.scratch_owner(device)
 
 
 def _seed_map_buffers(device: torch.device, n_cols: int):
@@ -1261,8 +1262,10 @@ _score_workspaces = {}
 
 
 def _score_workspace(device: torch.device, n_floats: int) -> Tensor:
-    """Per (device, stream): the score panel, allocated once and reused (grown when a request needs more)."""
-    key = _scratch_key(device)[:2]
+    """Per (device, stream, host thread): the score panel, allocated once and reused (grown when a request needs more).
+    lgc_score_rows fills it and lgc_mask_topk ranks it in a later launch: two threads on one stream (the default stream
+    of every thread) would otherwise rank each other's scores."""
+    key = _scratch_key(device)
     got = _score_workspaces.get(key)
     if got is None or got.numel() < n_floats:
         _score_workspaces.pop(key, None)
