@@ -57,9 +57,9 @@ __device__ __forceinline__ void write_candidate(int64_t *out_index, float *out_v
 
 // One wavefront merges the `total` places the slices left for one row at src: 64 at a time are appended to buf
 // ([kNbCapMax], the wavefront's own; empty places skipped), which is compacted to the k best whenever another 64 might not
-// fit.  The k best go to places o .. o + k - 1 of the result.
-__device__ __forceinline__ void merge_row(u64 *buf, const u64 *src, int total, int k, int lane, int64_t *out_index,
-                                          float *out_value, int64_t o) {
+// fit.  merge_keep leaves the best in buf[0, n), best first, and returns n <= k; merge_row writes them to places
+// o .. o + k - 1 of the result.
+__device__ __forceinline__ int merge_keep(u64 *buf, const u64 *src, int total, int k, int lane) {
     int n = 0;
     for (int base = 0; base < total; base += kWave) {
         const u64 e = base + lane < total ? src[base + lane] : 0ull;
@@ -68,7 +68,12 @@ __device__ __forceinline__ void merge_row(u64 *buf, const u64 *src, int total, i
         n += __popcll(have);
         if (n > kNbCapMax - kWave) n = compact_row(buf, n, k, lane, nullptr, nullptr);
     }
-    n = compact_row(buf, n, k, lane, nullptr, nullptr);
+    return compact_row(buf, n, k, lane, nullptr, nullptr);
+}
+
+__device__ __forceinline__ void merge_row(u64 *buf, const u64 *src, int total, int k, int lane, int64_t *out_index,
+                                          float *out_value, int64_t o) {
+    const int n = merge_keep(buf, src, total, k, lane);
     if (lane < k) write_candidate(out_index, out_value, o + lane, lane < n ? buf[lane] : 0ull);
 }
 

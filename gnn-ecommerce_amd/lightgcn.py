@@ -15,7 +15,8 @@ interaction lists (``foldin``); ``explain_topk`` and ``explain_sessions`` split 
 own items (``explain``); ``similar_items`` answers "which items are like this one?" (``similar``); ``recommend_diverse``,
 ``rerank_diverse`` and ``list_diversity`` re-rank a candidate list by greedy maximal marginal relevance and measure the
 intra-list diversity of the result (``rerank``); ``recommend_filtered``, ``item_audience`` and ``similar_users`` retrieve across
-two tables with a catalogue filter and per-request exclusion lists that REMOVE what they list (``retrieve``).  What changes is underneath: propagation is the HIP CSR-SpMM with
+two tables with a catalogue filter and per-request exclusion lists that REMOVE what they list (``retrieve``); ``bought_together`` answers "customers who bought this also bought" from the
+purchase lists alone, without the embedding (``cooccur``).  What changes is underneath: propagation is the HIP CSR-SpMM with
 the layer sum fused (``propagate.propagate_sum``) and pair scoring is one gather-dot kernel.
 """
 from __future__ import annotations
@@ -36,6 +37,7 @@ from .lgconv import LGConv
 from .paths import shortest_paths
 from .similar import METRICS, item_neighbors, row_rnorm
 from .retrieve import BuyerLists, request_lists, retrieve_topk
+from .cooccur import MEASURES, CoPurchase
 from .fullrank import evaluate_full_rank
 from .propagate import (DEFAULT_WORKSPACE_BYTES, TOPK_MAX, PositiveLists, RegHook, SeenLists, bpr_loss_fused, column_sums,
                         evaluate_ranking, evaluate_topk, mask_topk, pair_dot, propagate_sum, recommend_topk,
@@ -519,6 +521,41 @@ class LightGCN(torch.nn.Module):
         if user_ok is not None:
             user_ok = user_ok.to(dev).contiguous()
         return retrieve_topk(user_t, user_t, k, ids, scale, scale, user_ok, skip_id=ids)
+
+    # -- customers who bought this also bought -----------------------------------------------------
+    def bought_together(self, edge_index, edge_weight, n_users, n_items, item_ids=None, k: int = 10, measure: str = "cosine",
+                        min_count: int = 1, item_ok=None, seen=None):
+        """``(index int64 [n, k], value fp32 [n, k], count int32 [n, k])`` on the device: per item of ``item_ids`` (item
+        indices WITHOUT the ``n_users`` offset; None = the whole catalogue in order) the k items that share most buyers with
+        it, by ``measure`` ("count", "cosine" or "jaccard" over the buyer counts), and the number of shared buyers of each.
+        With ``seen`` (a ``SeenLists``) those purchase lists are used; without it every edge of ``edge_index`` (an int64
+        ``[2, E]`` tensor) is a purchase.  An item that shares fewer than ``min_count`` buyers, or whose ``item_ok`` entry
+        (bool or uint8 ``[n_items]``) is 0, is never returned; short rows end in -1 / -inf / 0.  It reads no embedding and
+        triggers no propagation: ``edge_weight`` is unused, and the answer is the same before the first training step.
+        The lists are transposed on every call; hold a ``cooccur.CoPurchase`` to ask many times.  See
+        ``cooccur.cooccur_topk``."""
+        n_users, n_items = int(n_users), int(n_items)
+        if n_users < 1 or n_items < 1 or n_users + n_items != self.num_nodes:
+            raise ValueError(f"n_users {n_users} + n_items {n_items} != {self.num_nodes} nodes")
+        if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= _native.COOCCUR_MAX_K:
+            raise ValueError(f"k must be an integer in [1, {_native.COOCCUR_MAX_K}]")
+        if not isinstance(measure, str) or measure not in MEASURES:
+            raise ValueError(f"measure must be one of {list(MEASURES)}, got {measure!r}")
+        if isinstance(min_count, bool) or not isinstance(min_count, int) or min_count < 1:
+            raise ValueError("min_count must be an integer of at least 1")
+        item_ok = self._ok_mask(item_ok, n_items, "item_ok")
+        ids = None if item_ids is None else self._id_tensor(item_ids, "item_ids")
+        if seen is not None:
+            if not isinstance(seen, SeenLists):
+                raise TypeError("seen must be a SeenLists or None")
+            _native.require_device(seen.ptr, "seen.ptr")
+            lists = CoPurchase.from_seen(seen, n_users, n_items)
+        else:
+            if not (torch.is_tensor(edge_index) and edge_index.dim() == 2):
+                raise ValueError("seen=None needs edge_index as an int64 [2, E] tensor (CoPurchase.from_edges)")
+            _native.require_device(edge_index, "edge_index")
+            lists = CoPurchase.from_edges(edge_index, n_users, n_items)
+        return lists.neighbors(ids, k, measure, min_count, item_ok)
 
     # -- k recommendations that are not k variants of one product ---------------------------------
     def _item_table(self, edge_index, edge_weight, n_users, n_items) -> Tensor:

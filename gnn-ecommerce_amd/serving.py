@@ -34,7 +34,12 @@ returns what upstream returns, ``[{'items': [[k item indices], ...]}]``.  What d
     does not combine with ``"explain"`` or ``"diversify"`` (``LightGCN.recommend_filtered``);
   * a body ``{"audience": [item ids], "k": int (optional, 1 .. 64, default 20), "deny_users": [user ids] (optional)}`` asks
     about ITEMS' audiences: it is answered with ``{"users": [[...]], "scores": [[...]]}``, per item the users who score it
-    best, its buyers and the denied users left out (``LightGCN.item_audience``).
+    best, its buyers and the denied users left out (``LightGCN.item_audience``);
+  * a body ``{"bought_together": [item ids], "k": int (optional, 1 .. 64, default 20), "measure": "count" | "cosine" |
+    "jaccard" (optional, default "cosine"), "min_count": int (optional, at least 1), "allow": [item ids] | "deny": [item ids]
+    (optional)}`` asks what is BOUGHT TOGETHER with items: it is answered with ``{"items": [[...]], "scores": [[...]],
+    "counts": [[...]]}``, per item the items that share most buyers with it, their scores and the numbers of shared buyers,
+    from the handler's purchase lists alone (``cooccur.CoPurchase``, built once at ``initialize``); the model is not asked.
 """
 from __future__ import annotations
 
@@ -49,6 +54,7 @@ from .graph import PropGraph
 from .lightgcn import LightGCN
 from .propagate import SeenLists
 from .retrieve import BuyerLists
+from .cooccur import MEASURES, CoPurchase
 from .rerank import check_lam
 from .similar import METRICS
 
@@ -91,6 +97,8 @@ class RecommendHandler:
         if self.graph.split is not None and self.graph.split != self.n_users:
             raise ValueError(f"{graph_path}: bipartite split {self.graph.split} != n_users {self.n_users}")
         self.seen = SeenLists(self.seen_ptr, self.seen_items).validate(self.n_users, graph_path + ": purchase lists")
+        self.copurchase = CoPurchase.from_seen(self.seen, self.n_users, self.n_items)
+        self.buyers = self.copurchase.buyers
         state = load_checkpoint(model_pt_path)
         hp = state["hyperparams"]
         self.model = LightGCN(self.n_users + self.n_items, hp["latent_dim"], hp["n_layers"])
@@ -303,6 +311,50 @@ class RecommendHandler:
         return {"users": [[row[j] for j in js] for row, js in zip(index, keep)],
                 "scores": [[row[j] for j in js] for row, js in zip(value, keep)]}
 
+    def parse_bought_together(self, body):
+        """``(item ids, k, measure, min_count, item_ok)`` of a body ``{"bought_together": [...], "k": optional, "measure":
+        optional, "min_count": optional, "allow" | "deny": optional}``; ``item_ok`` a host uint8 ``[n_items]`` tensor or None.
+        A malformed body raises ValueError, an id outside the catalogue IndexError."""
+        unknown = set(body) - {"bought_together", "k", "measure", "min_count", "allow", "deny"}
+        if unknown or "bought_together" not in body:
+            raise ValueError("request body: expected 'bought_together' and optionally 'k', 'measure', 'min_count', 'allow' or "
+                             f"'deny'; got {sorted(map(str, body))}")
+        if "allow" in body and "deny" in body:
+            raise ValueError("request body: 'allow' and 'deny' do not combine")
+        ids, k = self._id_list(body["bought_together"], "'bought_together'"), body.get("k", self.k)
+        if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= _native.COOCCUR_MAX_K:
+            raise ValueError(f"request body: 'k' must be an integer in [1, {_native.COOCCUR_MAX_K}]")
+        measure, min_count = body.get("measure", "cosine"), body.get("min_count", 1)
+        if not isinstance(measure, str) or measure not in MEASURES:
+            raise ValueError(f"request body: 'measure' must be one of {list(MEASURES)}")
+        if isinstance(min_count, bool) or not isinstance(min_count, int) or not 1 <= min_count < 2 ** 31:
+            raise ValueError("request body: 'min_count' must be an integer of at least 1")
+        item_ok = None
+        for name in ("allow", "deny"):
+            if name in body:
+                listed = self._id_list(body[name], f"'{name}'")
+                if any(i < 0 or i >= self.n_items for i in listed):
+                    raise IndexError(f"item index outside [0, {self.n_items})")
+                item_ok = torch.full((self.n_items,), 1 if name == "deny" else 0, dtype=torch.uint8)
+                item_ok[torch.tensor(listed, dtype=torch.int64)] = 0 if name == "deny" else 1
+        if any(i < 0 or i >= self.n_items for i in ids):
+            raise IndexError(f"item index outside [0, {self.n_items})")
+        return ids, k, measure, min_count, item_ok
+
+    def inference_bought_together(self, ids, k: int, measure: str, min_count: int, item_ok):
+        """Per asked-about item the ``k`` items that share most buyers with it, their scores and the shared buyers of each,
+        best first, from the purchase lists (transposed once); empty places dropped."""
+        if not ids:
+            return {"items": [], "scores": [], "counts": []}
+        if getattr(self, "copurchase", None) is None:
+            self.copurchase = CoPurchase.from_seen(self.seen, self.n_users, self.n_items)
+        index, value, count = self.copurchase.neighbors(ids, k, measure, min_count, item_ok)
+        index, value, count = index.cpu().tolist(), value.cpu().tolist(), count.cpu().tolist()
+        keep = [[j for j, i in enumerate(row) if i >= 0] for row in index]
+        return {"items": [[row[j] for j in js] for row, js in zip(index, keep)],
+                "scores": [[row[j] for j in js] for row, js in zip(value, keep)],
+                "counts": [[row[j] for j in js] for row, js in zip(count, keep)]}
+
     def parse_diversify(self, body):
         """``(requests, lam, candidates, metric)`` of a body ``{"requests": [...], "diversify": lam, "candidates": optional,
         "metric": optional}``.  A malformed body raises ValueError, a user id outside ``[0, n_users)`` IndexError."""
@@ -390,6 +442,8 @@ class RecommendHandler:
 
     def inference(self, data, *args, **kwargs):
         if isinstance(data, dict):
+            if "bought_together" in data:
+                return self.inference_bought_together(*self.parse_bought_together(data))
             if "similar" in data:
                 return self.inference_similar(*self.parse_similar(data))
             if "audience" in data:

@@ -1303,6 +1303,73 @@ int lgc_retrieve_topk(const float *queries, int64_t query_stride, int64_t n_quer
                       int64_t *out_index, float *out_value,
                       void *workspace, size_t workspace_bytes, int32_t *status, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Bought together (an addition to ABI 14: exports only): per query ITEM the k items that share most buyers with it --
+ * "customers who bought this also bought", the item-kNN baseline -- from the two purchase CSRs alone: no embedding, no
+ * training.  Counting, scoring and selection are one launch per band of the catalogue; the counts live in LDS and only
+ * those of the returned items are written out.
+ *
+ * lgc_cooccur_topk: per query item the k best eligible items.
+ *   buyer_ptr, buyer_users  item -> users: int64 [n_items + 1] and int64 entries (BuyerLists); n_items >= 1
+ *   seen_ptr, seen_items    user -> items: int64 [n_users + 1] and int64 entries (SeenLists, ingest.seen_csr)
+ *              Both ptr arrays are read on trust, as lgc_mask_topk and lgc_retrieve_topk read theirs.  Every ENTRY is
+ *              range-checked before an address is formed from it: a buyer outside [0, n_users) or an item outside
+ *              [0, n_items) is skipped and sets LGC_ST_INDEX_OOB in `status`.  The lists are ascending and distinct, as
+ *              BuyerLists and SeenLists build them.  A repeated entry counts as often as it occurs; an unsorted list gives
+ *              unspecified counts but never an access out of range
+ *   Count      for query item q and item j, c(q, j) = the sum over the entries u of q's buyer list of the number of entries of
+ *              u's item list equal to j.  a = buyer_ptr[q + 1] - buyer_ptr[q] and b the same for j: list lengths in entries.
+ *              Integer adds only (uint32 LDS atomics, whose order does not show); no float atomics anywhere: the same bytes on
+ *              every run.  With distinct lists c <= a < 2^31 - 1; a count that repeated entries push past 2^32 - 1 wraps
+ *   Eligible   item j is a candidate for q iff j != q, c >= min_count (min_count >= 1, LGC_E_RANGE otherwise: an item that
+ *              shares no buyer is never returned) and item_ok is NULL or item_ok[j] != 0 (uint8 [n_items])
+ *   Score      in fp32, every step rounded on its own (-ffp-contract=off), by `measure`:
+ *              LGC_COOCCUR_COUNT    s = (float)c, round to nearest even
+ *              LGC_COOCCUR_COSINE   ra = 1.0f / sqrtf((float)a), rb = 1.0f / sqrtf((float)b), the conversion, the root and the
+ *                                   division each correctly rounded (lgc_build_csr's recipe for deg^-1/2);
+ *                                   s = fl(fl((float)c * ra) * rb)
+ *              LGC_COOCCUR_JACCARD  s = (float)c / (float)(a + b - c): the integer formed in int64 and converted once, the
+ *                                   division correctly rounded.  With distinct lists the denominator is >= 1; where repeated
+ *                                   entries make it <= 0 the candidate is not eligible
+ *   Order      lgc_mask_topk's total order on (s, ascending j).  It is strict, so the result depends neither on `band` nor on
+ *              the order of arrival
+ *   query_ids  int64 [n_queries] items, any order, repeats allowed; NULL = query r is item r.  An id outside [0, n_items)
+ *              sets LGC_ST_INDEX_OOB and its row is -1 / -inf / 0; it is range-checked before any address is formed from it
+ *   k          1 .. LGC_COOCCUR_MAX_K
+ *   band       the item counters one workgroup holds in LDS: the catalogue is cut into ceil(n_items / band) bands, one
+ *              workgroup per (query, band), and a merge launch follows where there is more than one band.  0 = the library
+ *              chooses (16384); an explicit value is a multiple of 64 in [64, LGC_COOCCUR_MAX_BAND],
+ *              what the LDS budget allows (LGC_E_RANGE otherwise, as for a band that cuts the catalogue into more than 2^20
+ *              bands).  A band wider than the catalogue holds the catalogue, rounded up to 64.  It exists so that tests can cross band edges on small catalogues; it never changes a result
+ *   out_index  int64 [n_queries, k]; out_value fp32 [n_queries, k] or NULL; out_count int32 [n_queries, k] or NULL: the
+ *              count c of each returned item (with several bands the merge launch counts the k returned items again: a place
+ *              of the workspace has no room for a count).  A row with fewer than k candidates ends in -1 / -inf / 0
+ *   workspace  device memory of at least lgc_cooccur_workspace_bytes(n_queries, n_items, k, band, stream) bytes, 8-byte aligned:
+ *              n_queries * bands * k words of 8 bytes where there is more than one band, else 0; may be NULL where that is 0.
+ *              The size function returns 0 for sizes the call would refuse and grows monotonically in n_queries, n_items, k.
+ *              It takes the stream of the call it sizes, as every entry of this library that is not on the fixed list of
+ *              host-only queries does; it runs on the host, enqueues nothing and reads nothing through the handle (NULL is
+ *              fine): what it returns depends on its four sizes alone
+ * Errors before any launch, no output touched: LGC_E_INVAL (a null required pointer -- the four list arrays, out_index,
+ * status --, a negative n_queries or n_users, a measure that is none of the three); LGC_E_RANGE (k, band or min_count out of
+ * range, n_items < 1, n_items, n_users or n_queries >= 2^31 - 1); LGC_E_ALIGN (an int64 pointer or the workspace not 8-byte
+ * aligned, out_value, out_count or status not dword aligned); LGC_E_WORKSPACE (a workspace that is too small or missing).
+ * n_queries == 0 validates, launches nothing and returns 0.
+ * ------------------------------------------------------------------------------------- */
+#define LGC_COOCCUR_MAX_K 64
+#define LGC_COOCCUR_MAX_BAND 32768
+#define LGC_COOCCUR_COUNT   0
+#define LGC_COOCCUR_COSINE  1
+#define LGC_COOCCUR_JACCARD 2
+size_t lgc_cooccur_workspace_bytes(int64_t n_queries, int64_t n_items, int32_t k, int32_t band, void *stream);
+int lgc_cooccur_topk(const int64_t *buyer_ptr, const int64_t *buyer_users, int64_t n_items,
+                     const int64_t *seen_ptr, const int64_t *seen_items, int64_t n_users,
+                     const int64_t *query_ids, int64_t n_queries,
+                     const uint8_t *item_ok, int32_t min_count, int32_t measure,
+                     int32_t k, int32_t band,
+                     int64_t *out_index, float *out_value, int32_t *out_count,
+                     void *workspace, size_t workspace_bytes, int32_t *status, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
