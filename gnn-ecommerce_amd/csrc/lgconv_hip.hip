@@ -1346,10 +1346,69 @@ __global__ void k_build_tiles(const int32_t *__restrict__ rowptr, const lgc_entr
 //                        wave (shuffles) and waves in order through LDS: a fixed association;
 //   the other blocks     rows with a handful of slots (one per band): one LANE GROUP per row, slots in order --
 //                        four rows per wavefront at D=64.
+// EPI is the epilogue: which rows of other tables it loads for an output row (`load`: requested before the slot loads in
+// the lane-group branch, after the LDS reduction in the workgroup branch) and what `finish` makes of them and the sum;
+// EPI::Args is the kernel's last argument.  The body stands in the kernel itself and the two epilogues are instantiations of
+// it: as a shared device function called from two kernels it compiles to other code.
+//   EpilogueRow1 (lgc_apply)    y = a * acc + b * r, r optional (finish_row); no argument of its own
+//   EpilogueRow2 (lgc_apply2)   y = (b2 * r2 + b * r) + a * acc  -- the association of lgc_lincomb over the terms (b2, r2),
+//                               (b, r), (a, sum), so that an item step can write a layer sum in its place; r is required,
+//                               r2 is requested first
 template <int VEC>
+__device__ __forceinline__ void finish_row2(const SpmmArgs &p, const float b2, int64_t row, int c0, Acc<VEC> acc,
+                                            const Acc<VEC> &rv, const Acc<VEC> &r2v) {
+    if (p.a != 1.0f) {
+#pragma unroll
+        for (int i = 0; i < VEC; ++i) acc.v[i] = __fmul_rn(p.a, acc.v[i]);
+    }
+#pragma unroll
+    for (int i = 0; i < VEC; ++i)
+        acc.v[i] = __fadd_rn(__fadd_rn(__fmul_rn(b2, r2v.v[i]), __fmul_rn(p.b, rv.v[i])), acc.v[i]);
+    store_out<VEC, SpmmArgs>(p, row, c0, acc);
+}
+
+struct EpilogueRow1 {
+    struct Args {};
+    template <int VEC> struct Rows { Acc<VEC> rv; };
+    template <int VEC>
+    static __device__ __forceinline__ Rows<VEC> load(const SpmmArgs &p, const Args &, int32_t row, int c0) {
+        Rows<VEC> e;
+        e.rv.zero();
+        if (p.r != nullptr) e.rv = load_row<VEC>(p.r + (int64_t)row * p.r_stride + c0);
+        return e;
+    }
+    template <int VEC>
+    static __device__ __forceinline__ void finish(const SpmmArgs &p, const Args &, int64_t row, int c0, const Acc<VEC> &acc,
+                                                  const Rows<VEC> &e) {
+        finish_row<VEC, SpmmArgs>(p, row, c0, acc, e.rv);
+    }
+};
+
+struct EpilogueRow2 {
+    struct Args {
+        const float *r2;
+        int64_t r2_stride;
+        float b2;
+    };
+    template <int VEC> struct Rows { Acc<VEC> r2v, rv; };
+    template <int VEC>
+    static __device__ __forceinline__ Rows<VEC> load(const SpmmArgs &p, const Args &q, int32_t row, int c0) {
+        Rows<VEC> e;
+        e.r2v = load_row<VEC>(q.r2 + (int64_t)row * q.r2_stride + c0);
+        e.rv = load_row<VEC>(p.r + (int64_t)row * p.r_stride + c0);
+        return e;
+    }
+    template <int VEC>
+    static __device__ __forceinline__ void finish(const SpmmArgs &p, const Args &q, int64_t row, int c0, const Acc<VEC> &acc,
+                                                  const Rows<VEC> &e) {
+        finish_row2<VEC>(p, q.b2, row, c0, acc, e.rv, e.r2v);
+    }
+};
+
+template <int VEC, class EPI>
 __global__ __launch_bounds__(kBlock) void k_sweep_combine(SpmmArgs p, const lgc_multi_row *__restrict__ wide, int32_t n_wide,
                                                          const lgc_multi_row *__restrict__ multi, int32_t n_multi,
-                                                         const float *__restrict__ partials) {
+                                                         const float *__restrict__ partials, typename EPI::Args q) {
     __shared__ float wave_sum[(kBlock / kWave) * 256];
     const int lane = threadIdx.x & (kWave - 1);
     const int wv = threadIdx.x / kWave;
@@ -1398,20 +1457,17 @@ __global__ __launch_bounds__(kBlock) void k_sweep_combine(SpmmArgs p, const lgc_
 #pragma unroll
                 for (int i = 0; i < VEC; ++i) acc.v[i] = __fadd_rn(acc.v[i], wave_sum[o * 256 + l * VEC + i]);
             }
-            Acc<VEC> rv;
-            rv.zero();
-            if (p.r != nullptr) rv = load_row<VEC>(p.r + (int64_t)mr.row * p.r_stride + c0);
-            finish_row<VEC, SpmmArgs>(p, mr.row, c0, acc, rv);
+            const auto epi = EPI::template load<VEC>(p, q, mr.row, c0);   // (as an argument of finish it schedules differently)
+            EPI::template finish<VEC>(p, q, mr.row, c0, acc, epi);
         }
         return;
     }
     const int64_t m = (((int64_t)blockIdx.x - n_wide) * (kBlock / kWave) + wv) * groups + g;
     if (g >= groups || m >= n_multi) return;
     const lgc_multi_row mr = multi[m];
-    Acc<VEC> acc, rv;
+    Acc<VEC> acc;
     acc.zero();
-    rv.zero();
-    if (p.r != nullptr) rv = load_row<VEC>(p.r + (int64_t)mr.row * p.r_stride + c0);
+    const auto epi = EPI::template load<VEC>(p, q, mr.row, c0);
     // a row has one slot per band it touches (8 here) plus the cuts of long pieces: eight loads in flight, slots past
     // the row's end read as +0 (adding +0 never changes the sum: it cannot be -0 after its first add), so a row of up to
     // eight slots costs one memory round trip -- it used to be 4 + 4 and then one load at a time for the rest
@@ -1427,109 +1483,7 @@ __global__ __launch_bounds__(kBlock) void k_sweep_combine(SpmmArgs p, const lgc_
 #pragma unroll
             for (int i = 0; i < VEC; ++i) acc.v[i] = __fadd_rn(acc.v[i], t[j].v[i]);
     }
-    finish_row<VEC, SpmmArgs>(p, mr.row, c0, acc, rv);
-}
-
-// k_sweep_combine with a second epilogue row (lgc_apply2):  y = (b2 * r2 + b * r) + a * acc  -- the association of
-// lgc_lincomb over the terms (b2, r2), (b, r), (a, sum), so that an item step can write a layer sum in its place.  A kernel
-// of its own, the same sums in the same order, so that k_sweep_combine keeps its code for every other layer; r is required.
-struct EpilogueRow2 {
-    const float *r2;
-    int64_t r2_stride;
-    float b2;
-};
-
-template <int VEC>
-__device__ __forceinline__ void finish_row2(const SpmmArgs &p, const EpilogueRow2 &q, int64_t row, int c0, Acc<VEC> acc,
-                                            const Acc<VEC> &rv, const Acc<VEC> &r2v) {
-    if (p.a != 1.0f) {
-#pragma unroll
-        for (int i = 0; i < VEC; ++i) acc.v[i] = __fmul_rn(p.a, acc.v[i]);
-    }
-#pragma unroll
-    for (int i = 0; i < VEC; ++i)
-        acc.v[i] = __fadd_rn(__fadd_rn(__fmul_rn(q.b2, r2v.v[i]), __fmul_rn(p.b, rv.v[i])), acc.v[i]);
-    store_out<VEC, SpmmArgs>(p, row, c0, acc);
-}
-
-template <int VEC>
-__global__ __launch_bounds__(kBlock) void k_sweep_combine2(SpmmArgs p, const lgc_multi_row *__restrict__ wide, int32_t n_wide,
-                                                          const lgc_multi_row *__restrict__ multi, int32_t n_multi,
-                                                          const float *__restrict__ partials, EpilogueRow2 q) {
-    __shared__ float wave_sum[(kBlock / kWave) * 256];
-    const int lane = threadIdx.x & (kWave - 1);
-    const int wv = threadIdx.x / kWave;
-    const int groups = kWave / p.lpr;
-    const int g = lane / p.lpr;
-    const int l = lane - g * p.lpr;
-    const int c0 = lane_column<VEC>(l, p.dim);
-    const float *pb = partials + c0;
-    if ((int32_t)blockIdx.x < n_wide) {
-        const lgc_multi_row mr = wide[blockIdx.x];
-        const bool active = g < groups;
-        const int units = (kBlock / kWave) * groups;
-        Acc<VEC> acc;
-        acc.zero();
-        if (active) {
-            int32_t s = mr.slot_begin + wv * groups + g;
-            for (; s + 3 * units < mr.slot_end; s += 4 * units) {
-                Acc<VEC> t0 = load_row<VEC>(pb + (int64_t)s * p.dim);
-                Acc<VEC> t1 = load_row<VEC>(pb + (int64_t)(s + units) * p.dim);
-                Acc<VEC> t2 = load_row<VEC>(pb + (int64_t)(s + 2 * units) * p.dim);
-                Acc<VEC> t3 = load_row<VEC>(pb + (int64_t)(s + 3 * units) * p.dim);
-#pragma unroll
-                for (int i = 0; i < VEC; ++i)
-                    acc.v[i] = __fadd_rn(__fadd_rn(__fadd_rn(__fadd_rn(acc.v[i], t0.v[i]), t1.v[i]), t2.v[i]), t3.v[i]);
-            }
-            for (; s < mr.slot_end; s += units) {
-                Acc<VEC> t0 = load_row<VEC>(pb + (int64_t)s * p.dim);
-#pragma unroll
-                for (int i = 0; i < VEC; ++i) acc.v[i] = __fadd_rn(acc.v[i], t0.v[i]);
-            }
-        }
-        for (int j = 1; j < groups; ++j) {   // every lane executes the shuffles; group 0 keeps the wave's sum
-#pragma unroll
-            for (int i = 0; i < VEC; ++i) {
-                float other = __shfl_down(acc.v[i], j * p.lpr);
-                if (g == 0) acc.v[i] = __fadd_rn(acc.v[i], other);
-            }
-        }
-        if (active && g == 0) {
-#pragma unroll
-            for (int i = 0; i < VEC; ++i) wave_sum[wv * 256 + l * VEC + i] = acc.v[i];
-        }
-        __syncthreads();
-        if (wv == 0 && active && g == 0) {
-            for (int o = 1; o < kBlock / kWave; ++o) {
-#pragma unroll
-                for (int i = 0; i < VEC; ++i) acc.v[i] = __fadd_rn(acc.v[i], wave_sum[o * 256 + l * VEC + i]);
-            }
-            const Acc<VEC> r2v = load_row<VEC>(q.r2 + (int64_t)mr.row * q.r2_stride + c0);
-            const Acc<VEC> rv = load_row<VEC>(p.r + (int64_t)mr.row * p.r_stride + c0);
-            finish_row2<VEC>(p, q, mr.row, c0, acc, rv, r2v);
-        }
-        return;
-    }
-    const int64_t m = (((int64_t)blockIdx.x - n_wide) * (kBlock / kWave) + wv) * groups + g;
-    if (g >= groups || m >= n_multi) return;
-    const lgc_multi_row mr = multi[m];
-    Acc<VEC> acc;
-    acc.zero();
-    const Acc<VEC> r2v = load_row<VEC>(q.r2 + (int64_t)mr.row * q.r2_stride + c0);   // both rows requested before the slots
-    const Acc<VEC> rv = load_row<VEC>(p.r + (int64_t)mr.row * p.r_stride + c0);
-    for (int32_t s = mr.slot_begin; s < mr.slot_end; s += 8) {
-        Acc<VEC> t[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            t[j].zero();
-            if (s + j < mr.slot_end) t[j] = load_row<VEC>(pb + (int64_t)(s + j) * p.dim);
-        }
-#pragma unroll
-        for (int j = 0; j < 8; ++j)
-#pragma unroll
-            for (int i = 0; i < VEC; ++i) acc.v[i] = __fadd_rn(acc.v[i], t[j].v[i]);
-    }
-    finish_row2<VEC>(p, q, mr.row, c0, acc, rv, r2v);
+    EPI::template finish<VEC>(p, q, mr.row, c0, acc, epi);
 }
 
 // The columns of the listed rows get `value` in `mark` (lgc_seed_mark): the rows the seeded pull has to look at.  Every
@@ -1789,11 +1743,66 @@ __host__ __device__ inline int32_t sweep_sort_col(int32_t col, int home, const i
     return bound[home] + (int32_t)(((int64_t)col - bound[own]) * w_home / w_own);
 }
 
+// Whether wavefront w = ((round * (wpbr / 4) + j / 4) * nb + band) * 4 + j % 4 of a serpentine plan (round_order 2) walks
+// its band downwards: the odd rounds do, so that what the previous round touched last is touched first, while it is still in
+// the Infinity Cache (and, for a few microseconds, in L2)
+__host__ __device__ inline bool sweep_walks_down(int w, int nb, int wpbr) { return (((w / 4) / nb) / (wpbr / 4)) % 2 == 1; }
+
+// The padding entry of a step: a column out of every table's range, accumulator row `row_cap` (the dummy row)
+inline uint32_t sweep_pad_x(int row_cap) { return 0x00FFFFFFu | ((uint32_t)row_cap << 24); }
+
+// The rules of a sweep configuration, for both planners.  light_len apart, because lgc_sweep_dplan_create answers a bad one
+// with LGC_E_INVAL before it answers LGC_E_RANGE for the rest.  for_device: piece_cap <= 64 and lookahead <= 64 -- the device
+// planner's composite sort key keeps 8 bits for an entry's position in its piece (pieces hold up to 4 x piece_cap entries) and
+// its step builder's window is one wavefront; other settings -> the host planner
+bool sweep_light_len_ok(const lgc_sweep_cfg &cfg) {    // light rows come in pairs of bands: an even count (n_bands >= 1 below)
+    return cfg.light_len >= -1 && (cfg.light_len <= 0 || cfg.n_bands % 2 == 0);
+}
+
+bool sweep_cfg_ok(const lgc_sweep_cfg *cfg, bool for_device) {
+    return cfg && cfg->n_bands >= 1 && cfg->n_bands <= 64 && cfg->waves_per_band_round >= 4 && cfg->waves_per_band_round % 4 == 0 &&
+           cfg->row_cap >= 1 && cfg->row_cap <= 254 && cfg->piece_cap >= 1 && cfg->lookahead >= 4 &&
+           (cfg->groups == 0 || cfg->groups == 2 || cfg->groups == 4) && cfg->round_order >= 0 && cfg->round_order <= 2 &&
+           sweep_light_len_ok(*cfg) && (!for_device || (cfg->piece_cap <= 64 && cfg->lookahead <= 64));
+}
+
+// Phase A of both planners: band b = columns [out[b], out[b + 1]), ranges with (nearly) equal entry counts, from the column
+// histogram (NB + 1 bounds).  Without entries every band but the first is empty.
+void band_bounds(const int32_t *hist, int64_t n_cols, int32_t col_lo, int32_t col_hi, int64_t ne, int NB, int32_t *out) {
+    for (int b = 0; b <= NB; ++b) out[b] = col_hi;
+    out[0] = col_lo;
+    if (ne <= 0) return;
+    int64_t run = 0;
+    int b = 1;
+    for (int64_t c = 0; c < n_cols && b < NB; ++c) {
+        run += hist[c];
+        while (b < NB && run * NB >= ne * b) out[b++] = col_lo + (int32_t)c + 1;
+    }
+}
+
+// wave_slab_ptr (one entry per wavefront and the total) from every wavefront's step count, 32 steps to a slab; returns the
+// number of slabs, or -1 for one that does not fit 31 bits (LGC_E_RANGE)
+int64_t slab_ptr_prefix(const std::vector<int32_t> &wave_steps, std::vector<int32_t> &ptr) {
+    ptr.assign(wave_steps.size() + 1, 0);
+    int64_t n_slabs = 0;
+    for (size_t w = 0; w < wave_steps.size(); ++w) {
+        ptr[w] = (int32_t)n_slabs;
+        n_slabs += (wave_steps[w] + 31) / 32;
+    }
+    if (n_slabs >= INT32_MAX) return -1;
+    ptr.back() = (int32_t)n_slabs;
+    return n_slabs;
+}
+
+// threads of the host side of both planners: LGCN_PLAN_THREADS, else one per hardware thread
+unsigned plan_threads() {
+    if (const char *e = getenv("LGCN_PLAN_THREADS")) return (unsigned)atoi(e);
+    return std::thread::hardware_concurrency();
+}
+
 template <class F>
 void parallel_for(int64_t n, F &&f) {
-    unsigned nt = std::thread::hardware_concurrency();
-    if (const char *e = getenv("LGCN_PLAN_THREADS")) nt = (unsigned)atoi(e);
-    nt = std::max(1u, std::min(nt, 64u));
+    const unsigned nt = std::max(1u, std::min(plan_threads(), 64u));
     if (nt == 1 || n < 64) {
         f(0, n);
         return;
@@ -1810,9 +1819,7 @@ void parallel_for(int64_t n, F &&f) {
 // f(i) for i in [0, n), one thread per index (n is small: the bands of a sweep plan)
 template <class F>
 void parallel_each(int64_t n, F &&f) {
-    unsigned nt = std::thread::hardware_concurrency();
-    if (const char *e = getenv("LGCN_PLAN_THREADS")) nt = (unsigned)atoi(e);
-    if (nt <= 1 || n <= 1) {
+    if (plan_threads() <= 1 || n <= 1) {
         for (int64_t i = 0; i < n; ++i) f(i);
         return;
     }
@@ -1986,6 +1993,27 @@ int plan_pieces_and_deal(const std::vector<int32_t> &run_len, int64_t n_rows, in
     return 0;
 }
 
+// What a finished plan reports (lgc_sweep_*plan_dims), the same from both planners; steps and padding entries per wavefront
+template <class Pad>
+lgc_sweep_dims fill_dims(const lgc_sweep_cfg &cfg, const PlanPieces &pp, int64_t n_rows, int64_t ne, int64_t n_slabs,
+                         const std::vector<int32_t> &wave_steps, const std::vector<Pad> &wave_pad) {
+    lgc_sweep_dims d{};
+    d.n_bands = cfg.n_bands;
+    d.rounds = pp.rounds;
+    d.row_cap = cfg.row_cap;
+    d.piece_cap = pp.PCAP;
+    d.n_waves = pp.n_waves;
+    d.n_slabs = n_slabs;
+    d.groups = cfg.groups == 2 ? 2 : 4;
+    d.n_slots = (int64_t)pp.pieces.size();
+    d.n_rows = (int32_t)n_rows;
+    d.n_entries = ne;
+    for (const int32_t n : wave_steps) d.n_steps += n;
+    for (const Pad n : wave_pad) d.n_padding += n;
+    d.light_len = pp.light_len;
+    return d;
+}
+
 int sweep_plan_build(lgc_sweep_plan &pl, const int32_t *rowptr, const lgc_entry *entries, int32_t row_begin, int32_t row_end,
                      int32_t col_lo, int32_t col_hi, const lgc_sweep_cfg &cfg) {
     const int NB = cfg.n_bands, WPBR = cfg.waves_per_band_round, CAP = cfg.row_cap;
@@ -2009,16 +2037,8 @@ int sweep_plan_build(lgc_sweep_plan &pl, const int32_t *rowptr, const lgc_entry 
         if (c < col_lo || c >= col_hi) return LGC_E_INVAL;
         ++hist[c - col_lo];
     }
-    std::vector<int32_t> bound(NB + 1, col_hi);   // band b = columns [bound[b], bound[b+1])
-    bound[0] = col_lo;
-    {
-        int64_t run = 0;
-        int b = 1;
-        for (int32_t c = 0; c < col_hi - col_lo && b < NB; ++c) {
-            run += hist[c];
-            while (b < NB && run * NB >= ne * b && ne > 0) bound[b++] = col_lo + c + 1;
-        }
-    }
+    std::vector<int32_t> bound(NB + 1);           // band b = columns [bound[b], bound[b+1])
+    band_bounds(hist.data(), col_hi - col_lo, col_lo, col_hi, ne, NB, bound.data());
     lap("A bands (histogram)");
     // B. every row sorted by column (stable: equal columns keep edge order); run length of each (row, band)
     std::vector<lgc_entry> sorted((size_t)ne);
@@ -2044,16 +2064,16 @@ int sweep_plan_build(lgc_sweep_plan &pl, const int32_t *rowptr, const lgc_entry 
         const int rc = plan_pieces_and_deal(run_len, n_rows, row_begin, cfg, pp);
         if (rc != 0) return rc;
     }
-    const int PCAP = pp.PCAP, rounds = pp.rounds;
     std::vector<SweepPiece> &pieces = pp.pieces;
     pl.multi = pp.multi;
-    const int64_t n_pieces = (int64_t)pieces.size(), n_waves = pp.n_waves;
+    const int64_t n_waves = pp.n_waves;
     std::vector<std::vector<int32_t>> &wave_pieces = pp.wave_pieces;
     lap("C pieces -> waves");
     // D. per wave: merged column-sorted list -> conflict-free steps of 4 -> slabs of 32 steps
-    const uint32_t PAD_X = 0x00FFFFFFu | ((uint32_t)CAP << 24);    // out-of-range column, dummy accumulator row
+    const uint32_t PAD_X = sweep_pad_x(CAP);
     std::vector<std::vector<uint32_t>> wave_slabs((size_t)n_waves);
-    std::vector<int64_t> wave_steps((size_t)n_waves, 0), wave_pad((size_t)n_waves, 0);
+    std::vector<int32_t> wave_steps((size_t)n_waves, 0);      // (a wavefront's steps are at most the entries: 31 bits)
+    std::vector<int64_t> wave_pad((size_t)n_waves, 0);
     pl.wave_npieces.assign((size_t)n_waves, 0);
     pl.piece_slot.assign((size_t)n_waves * CAP, 0);
     const bool serpentine = cfg.round_order == 2;
@@ -2077,9 +2097,7 @@ int sweep_plan_build(lgc_sweep_plan &pl, const int32_t *rowptr, const lgc_entry 
                 }
             }
             std::stable_sort(items.begin(), items.end(), [](const Item &a, const Item &b) { return a.key < b.key; });
-            // odd rounds walk their band back down: what the previous round touched last is touched first, while it
-            // is still in the Infinity Cache (and, for a few microseconds, in L2)
-            if (serpentine && (((w / 4) / NB) / (WPBR / 4)) % 2 == 1) std::reverse(items.begin(), items.end());
+            if (serpentine && sweep_walks_down((int)w, NB, WPBR)) std::reverse(items.begin(), items.end());
             done.assign(items.size(), 0);
             size_t head = 0;
             int64_t step = 0, pad = 0;
@@ -2112,41 +2130,21 @@ int sweep_plan_build(lgc_sweep_plan &pl, const int32_t *rowptr, const lgc_entry 
                 pad += GROUPS - n_used;
                 ++step;
             }
-            wave_steps[(size_t)w] = step;
+            wave_steps[(size_t)w] = (int32_t)step;
             wave_pad[(size_t)w] = pad;
         }
     });
     lap("D steps and slabs per wave");
-    pl.wave_slab_ptr.assign((size_t)n_waves + 1, 0);
-    int64_t total = 0, n_steps_total = 0, n_pad = 0;
-    for (int64_t w = 0; w < n_waves; ++w) {
-        pl.wave_slab_ptr[(size_t)w] = (int32_t)(total / SLAB);
-        total += (int64_t)wave_slabs[(size_t)w].size();
-        n_steps_total += wave_steps[(size_t)w];
-        n_pad += wave_pad[(size_t)w];
-    }
-    if (total / SLAB >= INT32_MAX) return LGC_E_RANGE;
-    pl.wave_slab_ptr[(size_t)n_waves] = (int32_t)(total / SLAB);
-    pl.slabs.resize((size_t)total);                 // (zero-fill of ~85 MB: ~10 ms; the copies below overwrite all of it)
+    const int64_t n_slabs = slab_ptr_prefix(wave_steps, pl.wave_slab_ptr);
+    if (n_slabs < 0) return LGC_E_RANGE;
+    pl.slabs.resize((size_t)n_slabs * SLAB);        // (zero-fill of ~85 MB: ~10 ms; the copies below overwrite all of it)
     parallel_for(n_waves, [&](int64_t wlo, int64_t whi) {
         for (int64_t w = wlo; w < whi; ++w)
             std::copy(wave_slabs[(size_t)w].begin(), wave_slabs[(size_t)w].end(),
                       pl.slabs.begin() + (size_t)pl.wave_slab_ptr[(size_t)w] * SLAB);
     });
     lap("slab concatenation");
-    pl.dims.n_bands = NB;
-    pl.dims.rounds = rounds;
-    pl.dims.row_cap = CAP;
-    pl.dims.piece_cap = PCAP;
-    pl.dims.n_waves = n_waves;
-    pl.dims.n_slabs = total / SLAB;
-    pl.dims.groups = GROUPS;
-    pl.dims.n_slots = n_pieces;
-    pl.dims.n_rows = n_rows;
-    pl.dims.n_entries = ne;
-    pl.dims.n_steps = n_steps_total;
-    pl.dims.n_padding = n_pad;
-    pl.dims.light_len = pp.light_len;
+    pl.dims = fill_dims(cfg, pp, n_rows, ne, n_slabs, wave_steps, wave_pad);
     return 0;
 }
 
@@ -2285,7 +2283,7 @@ __global__ void k_dp_item_keys(const DpPiece *__restrict__ pieces, int64_t n_pie
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_pieces) return;
     const DpPiece pc = pieces[i];
-    const bool down = serpentine && (((pc.wave / 4) / nb) / (wpbr / 4)) % 2 == 1;
+    const bool down = serpentine && sweep_walks_down(pc.wave, nb, wpbr);
     const unsigned long long mask = (1ull << 40) - 1;
     const int home = (pc.wave / 4) % nb;
     for (int32_t j = 0; j < pc.count; ++j) {
@@ -2311,7 +2309,7 @@ __global__ __launch_bounds__(kBlock) void k_dp_steps(const unsigned long long *_
     const int w = blockIdx.x * (kBlock / kWave) + wib;
     if (w >= n_waves) return;                                     // wave-uniform
     const int32_t begin = wave_item_ptr[w], end = wave_item_ptr[w + 1];
-    const bool down = serpentine && (((w / 4) / nb) / (wpbr / 4)) % 2 == 1;
+    const bool down = serpentine && sweep_walks_down(w, nb, wpbr);
     const unsigned long long mask = (1ull << 40) - 1;
     const int slab_dwords = 64 * groups;
     uint32_t *cp_buf = buf_cp + wib * kWave, *v_buf = buf_v + wib * kWave;
@@ -2752,12 +2750,8 @@ lgc_sweep_plan *lgc_sweep_plan_create(const int32_t *rowptr_host, const lgc_entr
                                       int32_t row_end, int32_t col_lo, int32_t col_hi, const lgc_sweep_cfg *cfg, int *code) {
     int rc = LGC_E_INVAL;
     lgc_sweep_plan *pl = nullptr;
-    if (rowptr_host && (entries_host || rowptr_host[row_end] == rowptr_host[row_begin]) && cfg && row_begin >= 0 &&
-        row_end >= row_begin && col_lo >= 0 && col_hi > col_lo && col_hi <= 0xFFFFFF && cfg->n_bands >= 1 &&
-        cfg->n_bands <= 64 && cfg->waves_per_band_round >= 4 && cfg->waves_per_band_round % 4 == 0 && cfg->row_cap >= 1 &&
-        cfg->row_cap <= 254 && cfg->piece_cap >= 1 && cfg->lookahead >= 4 && (cfg->groups == 0 || cfg->groups == 2 || cfg->groups == 4) &&
-        cfg->round_order >= 0 && cfg->round_order <= 2 && cfg->light_len >= -1 &&
-        (cfg->light_len <= 0 || (cfg->n_bands >= 2 && cfg->n_bands % 2 == 0))) {
+    if (rowptr_host && (entries_host || rowptr_host[row_end] == rowptr_host[row_begin]) && row_begin >= 0 &&
+        row_end >= row_begin && col_lo >= 0 && col_hi > col_lo && col_hi <= 0xFFFFFF && sweep_cfg_ok(cfg, false)) {
         pl = new (std::nothrow) lgc_sweep_plan();
         if (pl) {
             try {
@@ -2865,16 +2859,10 @@ DplanWs dplan_carve(void *base, int64_t ne, int64_t n_rows, int64_t n_cols, cons
     return ws;
 }
 
-bool dplan_cfg_ok(const lgc_sweep_cfg *cfg) {
-    return cfg && cfg->n_bands >= 1 && cfg->n_bands <= 64 && cfg->waves_per_band_round >= 4 && cfg->waves_per_band_round % 4 == 0 &&
-           cfg->row_cap >= 1 && cfg->row_cap <= 254 && cfg->piece_cap >= 1 && cfg->piece_cap <= 64 && cfg->lookahead >= 4 &&
-           cfg->lookahead <= 64 && (cfg->groups == 0 || cfg->groups == 2 || cfg->groups == 4) && cfg->round_order >= 0 &&
-           cfg->round_order <= 2 && cfg->light_len >= -1 && (cfg->light_len <= 0 || cfg->n_bands % 2 == 0);
-}
 }  // namespace
 
 size_t lgc_sweep_dplan_workspace_bytes(int64_t n_entries, int64_t n_rows, int64_t n_cols, const lgc_sweep_cfg *cfg) {
-    if (!dplan_cfg_ok(cfg) || n_entries < 0 || n_rows < 0 || n_cols <= 0 || n_entries >= INT32_MAX) return 0;
+    if (!sweep_cfg_ok(cfg, true) || n_entries < 0 || n_rows < 0 || n_cols <= 0 || n_entries >= INT32_MAX) return 0;
     return dplan_carve(nullptr, n_entries, n_rows, n_cols, *cfg).total;
 }
 
@@ -2886,16 +2874,13 @@ lgc_sweep_dplan *lgc_sweep_dplan_create(const int32_t *rowptr, const lgc_entry *
         if (code) *code = rc;
         return nullptr;
     };
-    // piece_cap <= 64 and lookahead <= 64: the composite sort key keeps 8 bits for an entry's position in its piece (pieces
-    // hold up to 4 x piece_cap entries) and the step builder's window is one wavefront; other settings -> the host planner
-    if (cfg && (cfg->light_len < -1 || (cfg->light_len > 0 && cfg->n_bands % 2 != 0))) return fail(LGC_E_INVAL);
-    if (!dplan_cfg_ok(cfg)) return fail(LGC_E_RANGE);
+    if (cfg && !sweep_light_len_ok(*cfg)) return fail(LGC_E_INVAL);
+    if (!sweep_cfg_ok(cfg, true)) return fail(LGC_E_RANGE);
     if (!rowptr || row_begin < 0 || row_end < row_begin || first_entry < 0 || n_entries < 0 || col_lo < 0 || col_hi <= col_lo ||
         col_hi > 0xFFFFFF || n_entries >= INT32_MAX || (n_entries > 0 && (!entries || !workspace)))
         return fail(LGC_E_INVAL);
     const int64_t ne = n_entries, e0 = first_entry, n_rows = (int64_t)row_end - row_begin, n_cols = (int64_t)col_hi - col_lo;
     const int NB = cfg->n_bands, WPBR = cfg->waves_per_band_round, CAP = cfg->row_cap, GROUPS = cfg->groups == 2 ? 2 : 4;
-    const int SLAB = 64 * GROUPS;
     if (ne > 0) {
         if (workspace_bytes < lgc_sweep_dplan_workspace_bytes(ne, n_rows, n_cols, cfg)) return fail(LGC_E_WORKSPACE);
         if (!aligned_to(workspace, 256)) return fail(LGC_E_ALIGN);
@@ -2937,16 +2922,7 @@ lgc_sweep_dplan *lgc_sweep_dplan_create(const int32_t *rowptr, const lgc_entry *
             if (err == hipSuccess) err = hipStreamSynchronize(st);
             if (err != hipSuccess) return bail((int)err);
             if (bad) return bail(LGC_E_INVAL);                     // a column outside [col_lo, col_hi)
-            for (int b = 0; b <= NB; ++b) bound.b[b] = col_hi;
-            bound.b[0] = col_lo;
-            {
-                int64_t run = 0;
-                int b = 1;
-                for (int32_t c = 0; c < n_cols && b < NB; ++c) {
-                    run += hist[(size_t)c];
-                    while (b < NB && run * NB >= ne * b) bound.b[b++] = col_lo + c + 1;
-                }
-            }
+            band_bounds(hist.data(), n_cols, col_lo, col_hi, ne, NB, bound.b);
             hipLaunchKernelGGL(k_dp_gather, dim3(eb), dim3(kBlock), 0, st, entries, e0, ne, ws.keys_b, ws.idx_b, bound, NB, ws.sorted,
                                ws.run_len);
             err = hipMemcpyAsync(run_len.data(), ws.run_len, run_len.size() * 4, hipMemcpyDeviceToHost, st);
@@ -2991,44 +2967,22 @@ lgc_sweep_dplan *lgc_sweep_dplan_create(const int32_t *rowptr, const lgc_entry *
             while ((int64_t(1) << wave_bits) < n_waves) ++wave_bits;
             err = hipcub::DeviceRadixSort::SortPairs(ws.cub, cb, ws.keys_a, ws.keys_b, ws.idx_a, ws.idx_b, (int)ne, 0, 40 + wave_bits, st);
             if (err != hipSuccess) return bail((int)err);
-            const uint32_t pad_x = 0x00FFFFFFu | ((uint32_t)CAP << 24);
             hipLaunchKernelGGL((k_dp_steps<false>), dim3(ceil_div(n_waves, kBlock / kWave)), dim3(kBlock), 0, st, ws.keys_b, ws.idx_b,
-                               ws.sorted, ws.item_ptr, (int32_t)n_waves, GROUPS, cfg->lookahead, WPBR, NB, serp, pad_x, ws.steps, ws.pad,
-                               (const int32_t *)nullptr, (uint32_t *)nullptr);
+                               ws.sorted, ws.item_ptr, (int32_t)n_waves, GROUPS, cfg->lookahead, WPBR, NB, serp, sweep_pad_x(CAP), ws.steps,
+                               ws.pad, (const int32_t *)nullptr, (uint32_t *)nullptr);
             err = hipMemcpyAsync(steps.data(), ws.steps, steps.size() * 4, hipMemcpyDeviceToHost, st);
             if (err == hipSuccess) err = hipMemcpyAsync(pads.data(), ws.pad, pads.size() * 4, hipMemcpyDeviceToHost, st);
             if (err == hipSuccess) err = hipStreamSynchronize(st);
             if (err != hipSuccess) return bail((int)err);
         }
-        pl->wave_slab_ptr.assign((size_t)n_waves + 1, 0);
-        int64_t n_slabs = 0, n_steps = 0, n_pad = 0;
-        for (int64_t w = 0; w < n_waves; ++w) {
-            pl->wave_slab_ptr[(size_t)w] = (int32_t)n_slabs;
-            n_slabs += (steps[(size_t)w] + 31) / 32;
-            n_steps += steps[(size_t)w];
-            n_pad += pads[(size_t)w];
-        }
-        if (n_slabs >= INT32_MAX) return bail(LGC_E_RANGE);
-        pl->wave_slab_ptr[(size_t)n_waves] = (int32_t)n_slabs;
+        const int64_t n_slabs = slab_ptr_prefix(steps, pl->wave_slab_ptr);
+        if (n_slabs < 0) return bail(LGC_E_RANGE);
         pl->keys = ws.keys_b;
         pl->idx = ws.idx_b;
         pl->sorted = ws.sorted;
         pl->d_item_ptr = ws.item_ptr;
         pl->d_slab_ptr = ws.slab_ptr;
-        pl->dims.n_bands = NB;
-        pl->dims.rounds = pp.rounds;
-        pl->dims.row_cap = CAP;
-        pl->dims.piece_cap = pp.PCAP;
-        pl->dims.n_waves = n_waves;
-        pl->dims.n_slabs = n_slabs;
-        pl->dims.groups = GROUPS;
-        pl->dims.n_slots = n_pieces;
-        pl->dims.n_rows = (int32_t)n_rows;
-        pl->dims.n_entries = ne;
-        pl->dims.n_steps = n_steps;
-        pl->dims.n_padding = n_pad;
-        pl->dims.light_len = pp.light_len;
-        (void)SLAB;
+        pl->dims = fill_dims(*cfg, pp, n_rows, ne, n_slabs, steps, pads);
     } catch (const std::bad_alloc &) {
         return bail((int)hipErrorOutOfMemory);
     }
@@ -3062,11 +3016,10 @@ int lgc_sweep_dplan_fill(const lgc_sweep_dplan *plan, uint32_t *slabs, int32_t *
     const lgc_sweep_cfg &cfg = plan->cfg;
     const int64_t n_waves = plan->dims.n_waves;
     if (n_waves > 0 && plan->dims.n_entries > 0) {
-        const uint32_t pad_x = 0x00FFFFFFu | ((uint32_t)cfg.row_cap << 24);
         hipLaunchKernelGGL((k_dp_steps<true>), dim3(ceil_div(n_waves, kBlock / kWave)), dim3(kBlock), 0, st, plan->keys, plan->idx,
                            plan->sorted, plan->d_item_ptr, (int32_t)n_waves, plan->dims.groups, cfg.lookahead,
-                           cfg.waves_per_band_round, cfg.n_bands, cfg.round_order == 2 ? 1 : 0, pad_x, (int32_t *)nullptr,
-                           (int32_t *)nullptr, (const int32_t *)wave_slab_ptr, slabs);
+                           cfg.waves_per_band_round, cfg.n_bands, cfg.round_order == 2 ? 1 : 0, sweep_pad_x(cfg.row_cap),
+                           (int32_t *)nullptr, (int32_t *)nullptr, (const int32_t *)wave_slab_ptr, slabs);
     }
     rc = (int)hipGetLastError();
     if (rc != 0) return rc;
@@ -3093,28 +3046,27 @@ int lgc_sweep_ok(int32_t dim, int64_t table_rows, int64_t x_stride) {
 }
 
 // lgc_spmm_sweep, and with r2 (lgc_apply2) its combine with the second epilogue row: y = (b2 * r2 + b * r) + a * A x
-static int spmm_sweep(const uint32_t *slabs, const int32_t *wave_slab_ptr, const int32_t *wave_npieces, const int32_t *piece_slot,
-                      int64_t n_waves, int32_t row_cap, int32_t groups, const lgc_multi_row *multi, int32_t n_rows,
-                      const lgc_multi_row *multi_wide, int32_t n_wide, float *partials,
-                      int64_t table_rows, const float *x, int64_t x_stride, float *y, int64_t y_stride, const float *r,
-                      int64_t r_stride, const float *r2, int64_t r2_stride, float a, float b, float b2, int32_t dim,
-                      void *stream_) {
+static int spmm_sweep(const lgc_sweep_arrays &sw, int64_t table_rows, const float *x, int64_t x_stride, float *y, int64_t y_stride,
+                      const float *r, int64_t r_stride, const float *r2, int64_t r2_stride, float a, float b, float b2,
+                      int32_t dim, void *stream_) {
+    const int64_t n_waves = sw.n_waves;
+    const int32_t n_rows = sw.n_rows, n_wide = sw.n_wide, groups = sw.groups == 0 ? 4 : sw.groups;
+    float *const partials = sw.partials;
     if (r2 && (!r || r2_stride < dim)) return LGC_E_INVAL;
     if (r2 && !aligned_to(r2, 4)) return LGC_E_ALIGN;
-    if (!slabs || !wave_slab_ptr || !wave_npieces || !piece_slot || !partials || !x || !y || n_waves < 0 ||
-        n_waves % 4 != 0 || n_rows < 0 || n_wide < 0 || (n_rows > 0 && !multi) || (n_wide > 0 && !multi_wide) || row_cap < 1 ||
-        row_cap > 254 || x == y)
+    if (!sw.slabs || !sw.wave_slab_ptr || !sw.wave_npieces || !sw.piece_slot || !partials || !x || !y || n_waves < 0 ||
+        n_waves % 4 != 0 || n_rows < 0 || n_wide < 0 || (n_rows > 0 && !sw.multi) || (n_wide > 0 && !sw.multi_wide) ||
+        sw.row_cap < 1 || sw.row_cap > 254 || x == y)
         return LGC_E_INVAL;
-    if (groups == 0) groups = 4;
     if (lgc_sweep_ok(dim, table_rows, x_stride) != groups) return LGC_E_DIM;    // the plan's step width must fit the table
     if (const int rc = check_tables(x, x_stride, y, y_stride, r, r_stride, dim)) return rc;
-    if (!aligned_to(slabs, 16) || !aligned_to(partials, 16)) return LGC_E_ALIGN;
+    if (!aligned_to(sw.slabs, 16) || !aligned_to(partials, 16)) return LGC_E_ALIGN;
     hipStream_t stream = as_stream(stream_);
-    const size_t lds = (size_t)(kBlock / kWave) * (size_t)(row_cap + 1) * (groups == 2 ? kWideRow : 64) * sizeof(float);
+    const size_t lds = (size_t)(kBlock / kWave) * (size_t)(sw.row_cap + 1) * (groups == 2 ? kWideRow : 64) * sizeof(float);
     if (lds > 160 * 1024) return LGC_E_INVAL;
     if (n_waves > 0) {
-        SweepArgs p{reinterpret_cast<const u4 *>(slabs), wave_slab_ptr, wave_npieces, piece_slot, x, partials, x_stride,
-                    (uint32_t)table_bytes(table_rows, x_stride, dim), dim, row_cap, (int32_t)n_waves, 0, nullptr, dim, 0};
+        SweepArgs p{reinterpret_cast<const u4 *>(sw.slabs), sw.wave_slab_ptr, sw.wave_npieces, sw.piece_slot, x, partials, x_stride,
+                    (uint32_t)table_bytes(table_rows, x_stride, dim), dim, sw.row_cap, (int32_t)n_waves, 0, nullptr, dim, 0};
         const bool two_pass = groups == 4 && dim > 64;   // columns [0, 64) and [64, dim) as two sweeps of the same plan
         if (two_pass) {
             p.dim = 64;
@@ -3152,10 +3104,11 @@ static int spmm_sweep(const uint32_t *slabs, const int32_t *wave_slab_ptr, const
         const int rows_per_block = (kBlock / kWave) * (kWave / cfg.lpr);
         const dim3 grid(n_wide + ceil_div(n_rows, rows_per_block));
         if (r2)
-            hipLaunchKernelGGL((k_sweep_combine2<4>), grid, dim3(kBlock), 0, stream, sp, multi_wide, n_wide, multi, n_rows, partials,
-                               EpilogueRow2{r2, r2_stride, b2});
+            hipLaunchKernelGGL((k_sweep_combine<4, EpilogueRow2>), grid, dim3(kBlock), 0, stream, sp, sw.multi_wide, n_wide, sw.multi,
+                               n_rows, partials, EpilogueRow2::Args{r2, r2_stride, b2});
         else
-            hipLaunchKernelGGL((k_sweep_combine<4>), grid, dim3(kBlock), 0, stream, sp, multi_wide, n_wide, multi, n_rows, partials);
+            hipLaunchKernelGGL((k_sweep_combine<4, EpilogueRow1>), grid, dim3(kBlock), 0, stream, sp, sw.multi_wide, n_wide, sw.multi,
+                               n_rows, partials, EpilogueRow1::Args{});
     }
     return (int)hipGetLastError();
 }
@@ -3165,8 +3118,9 @@ int lgc_spmm_sweep(const uint32_t *slabs, const int32_t *wave_slab_ptr, const in
                    const lgc_multi_row *multi_wide, int32_t n_wide, float *partials,
                    int64_t table_rows, const float *x, int64_t x_stride, float *y, int64_t y_stride, const float *r,
                    int64_t r_stride, float a, float b, int32_t dim, void *stream_) {
-    return spmm_sweep(slabs, wave_slab_ptr, wave_npieces, piece_slot, n_waves, row_cap, groups, multi, n_rows, multi_wide, n_wide,
-                      partials, table_rows, x, x_stride, y, y_stride, r, r_stride, nullptr, 0, a, b, 0.0f, dim, stream_);
+    const lgc_sweep_arrays sw{slabs, wave_slab_ptr, wave_npieces, piece_slot, multi, multi_wide, partials, n_waves, row_cap, n_rows,
+                              n_wide, groups};
+    return spmm_sweep(sw, table_rows, x, x_stride, y, y_stride, r, r_stride, nullptr, 0, a, b, 0.0f, dim, stream_);
 }
 
 int lgc_apply_route(const lgc_operator *op, int64_t table_rows, int64_t x_stride, int64_t y_stride, int64_t r_stride,
@@ -3198,12 +3152,8 @@ int lgc_apply(const lgc_operator *op, int64_t table_rows, const float *x, int64_
     switch (route & ~LGC_ROUTE_WT_STORE) {
     case LGC_ROUTE_SWEEP:
     case LGC_ROUTE_SWEEP_WIDE:
-    case LGC_ROUTE_SWEEP_TWO_PASS: {
-        const lgc_sweep_arrays *sw = op->sweep;
-        return lgc_spmm_sweep(sw->slabs, sw->wave_slab_ptr, sw->wave_npieces, sw->piece_slot, sw->n_waves, sw->row_cap,
-                              sw->groups, sw->multi, sw->n_rows, sw->multi_wide, sw->n_wide, sw->partials, table_rows, x, x_stride, y,
-                              y_stride, r, r_stride, a, b, dim, stream);
-    }
+    case LGC_ROUTE_SWEEP_TWO_PASS:
+        return spmm_sweep(*op->sweep, table_rows, x, x_stride, y, y_stride, r, r_stride, nullptr, 0, a, b, 0.0f, dim, stream);
     case LGC_ROUTE_FUSED_DPP:
     case LGC_ROUTE_FUSED_GENERIC: {
         // one launch: [chunk workgroups | tile classes], then the fixed-order combine of rows cut into several chunks
@@ -3280,12 +3230,8 @@ int lgc_apply2(const lgc_operator *op, int64_t table_rows, const float *x, int64
     switch (route & ~LGC_ROUTE_WT_STORE) {
     case LGC_ROUTE_SWEEP:
     case LGC_ROUTE_SWEEP_WIDE:
-    case LGC_ROUTE_SWEEP_TWO_PASS: {
-        const lgc_sweep_arrays *sw = op->sweep;
-        return spmm_sweep(sw->slabs, sw->wave_slab_ptr, sw->wave_npieces, sw->piece_slot, sw->n_waves, sw->row_cap, sw->groups,
-                          sw->multi, sw->n_rows, sw->multi_wide, sw->n_wide, sw->partials, table_rows, x, x_stride, y, y_stride, r,
-                          r_stride, r2, r2_stride, a, b, b2, dim, stream);
-    }
+    case LGC_ROUTE_SWEEP_TWO_PASS:
+        return spmm_sweep(*op->sweep, table_rows, x, x_stride, y, y_stride, r, r_stride, r2, r2_stride, a, b, b2, dim, stream);
     default:
         return LGC_E_DIM;     // no sweep for this operator and table (as lgc_spmm_sweep): tiles, chunks and rows keep one row
     }

@@ -327,6 +327,31 @@ def _sweep_plan_create(rowptr: Tensor, entries: Tensor, row_begin: int, row_end:
     return handle, d
 
 
+def _sweep_dims(d) -> dict:
+    return {k: getattr(d, k) for k, _ in _native.SweepDims._fields_ if k != "reserved"}
+
+
+def _sweep_arrays(d, device) -> Tuple[Dict[str, Tensor], List[int]]:
+    """The five arrays of a plan of dims ``d``, unwritten and never empty -- the four big ones on ``device``, ``multi``
+    on the host, where SweepPlan splits it by slot count -- and the addresses of the four, in the planners' order."""
+    i32 = dict(dtype=torch.int32, device=device)
+    arrays = {"slabs": torch.empty(max(d.n_slabs, 1) * 64 * d.groups, **i32),
+              "wave_slab_ptr": torch.empty(d.n_waves + 1, **i32),
+              "wave_npieces": torch.empty(max(d.n_waves, 1), **i32),
+              "piece_slot": torch.empty(max(d.n_waves * d.row_cap, 1), **i32)}
+    ptrs = [t.data_ptr() for t in arrays.values()]
+    arrays["multi"] = torch.empty((max(d.n_rows, 1), 4), dtype=torch.int32)
+    return arrays, ptrs
+
+
+def _sweep_result(d, arrays: Dict[str, Tensor], row_offset: int) -> Tuple[dict, Dict[str, Tensor]]:
+    """(dims, arrays), ``multi`` cut to the plan's rows and its row ids moved by ``row_offset``: the host planner numbers
+    the rows of its slice from 0, the device planner returns the CSR's own row ids (offset 0)."""
+    arrays["multi"] = arrays["multi"][:d.n_rows].contiguous()
+    arrays["multi"][:, 0] += row_offset
+    return _sweep_dims(d), arrays
+
+
 def sweep_plan_host(rowptr: Tensor, entries: Tensor, row_begin: int, row_end: int, col_lo: int, col_hi: int,
                     cfg: Optional[dict] = None) -> Tuple[dict, Dict[str, Tensor]]:
     """Run the host planner (lgc_sweep_plan_*) on rows [row_begin, row_end) of a CSR given as tensors on any device;
@@ -334,20 +359,11 @@ def sweep_plan_host(rowptr: Tensor, entries: Tensor, row_begin: int, row_end: in
     lib = _native.load()
     handle, d = _sweep_plan_create(rowptr, entries, row_begin, row_end, col_lo, col_hi, cfg)
     try:
-        dims = {k: getattr(d, k) for k, _ in _native.SweepDims._fields_ if k != "reserved"}
-        arrays = {"slabs": torch.empty(max(d.n_slabs, 1) * 64 * d.groups, dtype=torch.int32),
-                  "wave_slab_ptr": torch.empty(d.n_waves + 1, dtype=torch.int32),
-                  "wave_npieces": torch.empty(max(d.n_waves, 1), dtype=torch.int32),
-                  "piece_slot": torch.empty(max(d.n_waves * d.row_cap, 1), dtype=torch.int32),
-                  "multi": torch.empty((max(d.n_rows, 1), 4), dtype=torch.int32)}
-        _native.check(lib.lgc_sweep_plan_export(handle, *(arrays[k].data_ptr() for k in
-                                                          ("slabs", "wave_slab_ptr", "wave_npieces", "piece_slot", "multi"))),
-                      "lgc_sweep_plan_export")
+        arrays, ptrs = _sweep_arrays(d, "cpu")
+        _native.check(lib.lgc_sweep_plan_export(handle, *ptrs, arrays["multi"].data_ptr()), "lgc_sweep_plan_export")
     finally:
         lib.lgc_sweep_plan_free(handle)
-    arrays["multi"] = arrays["multi"][:d.n_rows].contiguous()
-    arrays["multi"][:, 0] += row_begin                 # the planner saw rows 0 .. n of the slice
-    return dims, arrays
+    return _sweep_result(d, arrays, row_begin)
 
 
 def sweep_plan_device(rowptr: Tensor, entries: Tensor, row_begin: int, row_end: int, col_lo: int, col_hi: int,
@@ -358,23 +374,13 @@ def sweep_plan_device(rowptr: Tensor, entries: Tensor, row_begin: int, row_end: 
     dev = rowptr.device
     handle, d = _sweep_plan_create(rowptr, entries, row_begin, row_end, col_lo, col_hi, cfg)
     try:
-        dims = {k: getattr(d, k) for k, _ in _native.SweepDims._fields_ if k != "reserved"}
-        i32 = dict(dtype=torch.int32, device=dev)
-        arrays = {"slabs": torch.empty(max(d.n_slabs, 1) * 64 * d.groups, **i32),
-                  "wave_slab_ptr": torch.empty(d.n_waves + 1, **i32),
-                  "wave_npieces": torch.empty(max(d.n_waves, 1), **i32),
-                  "piece_slot": torch.empty(max(d.n_waves * d.row_cap, 1), **i32),
-                  "multi": torch.empty((max(d.n_rows, 1), 4), dtype=torch.int32)}
+        arrays, ptrs = _sweep_arrays(d, dev)
         with torch.cuda.device(dev):
-            _native.check(lib.lgc_sweep_plan_upload(handle, *(arrays[k].data_ptr() for k in
-                                                              ("slabs", "wave_slab_ptr", "wave_npieces", "piece_slot")),
-                                                    _native.stream_of(dev)), "lgc_sweep_plan_upload")
+            _native.check(lib.lgc_sweep_plan_upload(handle, *ptrs, _native.stream_of(dev)), "lgc_sweep_plan_upload")
         _native.check(lib.lgc_sweep_plan_export_multi(handle, arrays["multi"].data_ptr()), "lgc_sweep_plan_export_multi")
     finally:
         lib.lgc_sweep_plan_free(handle)
-    arrays["multi"] = arrays["multi"][:d.n_rows].contiguous()
-    arrays["multi"][:, 0] += row_begin
-    return dims, arrays
+    return _sweep_result(d, arrays, row_begin)
 
 
 def sweep_plan_on_device(rowptr: Tensor, entries: Tensor, row_begin: int, row_end: int, col_lo: int, col_hi: int,
@@ -406,25 +412,16 @@ def sweep_plan_on_device(rowptr: Tensor, entries: Tensor, row_begin: int, row_en
     try:
         d = _native.SweepDims()
         _native.check(lib.lgc_sweep_dplan_dims(handle, ctypes.byref(d)), "lgc_sweep_dplan_dims")
-        dims = {k: getattr(d, k) for k, _ in _native.SweepDims._fields_ if k != "reserved"}
-        i32 = dict(dtype=torch.int32, device=dev)
-        arrays = {"slabs": torch.empty(max(d.n_slabs, 1) * 64 * d.groups, **i32),
-                  "wave_slab_ptr": torch.empty(d.n_waves + 1, **i32),
-                  "wave_npieces": torch.empty(max(d.n_waves, 1), **i32),
-                  "piece_slot": torch.empty(max(d.n_waves * d.row_cap, 1), **i32),
-                  "multi": torch.empty((max(d.n_rows, 1), 4), dtype=torch.int32)}
+        arrays, ptrs = _sweep_arrays(d, dev)
         with torch.cuda.device(dev):
-            _native.check(lib.lgc_sweep_dplan_fill(handle, *(arrays[k].data_ptr() for k in
-                                                             ("slabs", "wave_slab_ptr", "wave_npieces", "piece_slot")),
-                                                   _native.stream_of(dev)), "lgc_sweep_dplan_fill")
+            _native.check(lib.lgc_sweep_dplan_fill(handle, *ptrs, _native.stream_of(dev)), "lgc_sweep_dplan_fill")
         _native.check(lib.lgc_sweep_dplan_export_multi(handle, arrays["multi"].data_ptr()), "lgc_sweep_dplan_export_multi")
     finally:
         lib.lgc_sweep_dplan_free(handle)
     del ws
-    arrays["multi"] = arrays["multi"][:d.n_rows].contiguous()
     if PLAN_TIMING:
         print(f"[plan] sweep plan on the device: {time.perf_counter() - t0:.3f} s", flush=True)
-    return dims, arrays
+    return _sweep_result(d, arrays, 0)
 
 
 SWEEP_PLAN_ON_DEVICE = os.environ.get("LGCN_SWEEP_PLAN_ON_DEVICE", "1") == "1"

@@ -432,8 +432,8 @@ int lgc_apply(const lgc_operator *op, int64_t table_rows, const float *x, int64_
  *     y[row] = (b2 * r2[row] + b * r[row]) + a * (A x)[row]
  * every product rounded before its add, in this association -- the bits of lgc_apply(x, t) followed by
  * lgc_lincomb(y, {(b2, r2), (b, r), (a, t)}), without the table t and the second launch: the item step before the last
- * layer writes the layer sum the last user step gathers (bipartite_sum).  The sweep runs as in lgc_apply; the combine is a
- * kernel of its own (k_sweep_combine2).  r and r2 are both required (LGC_E_INVAL for either missing or a stride below dim,
+ * layer writes the layer sum the last user step gathers (bipartite_sum).  The sweep runs as in lgc_apply; the combine is
+ * k_sweep_combine with the two-row epilogue.  r and r2 are both required (LGC_E_INVAL for either missing or a stride below dim,
  * LGC_E_ALIGN for one that is not dword aligned); r may alias y as in lgc_apply (a lane reads the elements it then writes),
  * r2 may too.  The route is asked of lgc_apply_route first: its errors come back unchanged, and an operator that would not take
  * LGC_ROUTE_SWEEP / _SWEEP_WIDE / _SWEEP_TWO_PASS at this geometry is refused with LGC_E_DIM before anything is launched.

@@ -1,4 +1,4 @@
-"""The layer sum written by the item step before the last layer (LGCN_MIX_IN_ITEM_STEP, lgc_apply2, k_sweep_combine2).
+"""The layer sum written by the item step before the last layer (LGCN_MIX_IN_ITEM_STEP, lgc_apply2, the two-row combine).
 
 One graph, 600 users x 40 items, whose item half runs as a FORCED band sweep under a small planner configuration: item
 HUB is in every user's list (600 entries, cut into more than 32 partial slots: the workgroup-per-row branch of the
