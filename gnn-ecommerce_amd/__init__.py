@@ -20,6 +20,7 @@ from .sampler import TripleSampler
 from .similar import item_neighbors, row_rnorm
 from .retrieve import BuyerLists, retrieve_topk
 from .cooccur import CoPurchase, cooccur_topk
+from .itemknn import ItemKNN, knn_recommend
 from .fullrank import FullRankResult, PairRanks, evaluate_full_rank, positive_ranks
 from .rerank import list_diversity, mmr_rerank
 from .softmax import SoftmaxBatch, softmax_batch, softmax_from_table, softmax_loss_reference
@@ -31,6 +32,6 @@ __all__ = ["LightGCN", "BPRLoss", "LGConv", "PropGraph", "get_graph", "clear_cac
            "SeenLists", "PositiveLists", "score_rows", "recommend_topk", "hop_distances", "shortest_paths", "paths_frame", "compute_paths",
            "rank_metrics", "evaluate_ranking", "overlap_items", "metrics_frame", "RankingResult",
            "SessionLists", "fold_table", "fold_in", "Attribution", "attribute",
-           "item_neighbors", "row_rnorm", "retrieve_topk", "BuyerLists", "cooccur_topk", "CoPurchase", "mmr_rerank", "list_diversity",
+           "item_neighbors", "row_rnorm", "retrieve_topk", "BuyerLists", "cooccur_topk", "CoPurchase", "knn_recommend", "ItemKNN", "mmr_rerank", "list_diversity",
            "positive_ranks", "evaluate_full_rank", "PairRanks", "FullRankResult",
            "softmax_batch", "softmax_loss_reference", "softmax_from_table", "SoftmaxBatch"]

@@ -221,6 +221,10 @@ SIGNATURES = {
     "lgc_cooccur_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int32, c_int32, c_void_p]),
     "lgc_cooccur_topk": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int32,
                                  c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "lgc_knn_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int32, c_int32, c_void_p]),
+    "lgc_knn_recommend": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_void_p,
+                                  c_int64, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
+                                  c_size_t, c_void_p, c_void_p]),
 }
 
 
@@ -305,6 +309,9 @@ RETRIEVE_MAX_K = 64    # LGC_RETRIEVE_MAX_K
 RETRIEVE_MAX_SLICES = 1024   # LGC_RETRIEVE_MAX_SLICES
 COOCCUR_MAX_K = 64     # LGC_COOCCUR_MAX_K
 COOCCUR_MAX_BAND = 32768   # LGC_COOCCUR_MAX_BAND: item counters of one workgroup
+KNN_MAX_K = 64         # LGC_KNN_MAX_K
+KNN_MAX_NEIGHBORS = 64 # LGC_KNN_MAX_NEIGHBORS: the widest neighbour table lgc_knn_recommend takes
+KNN_MAX_BAND = 16384   # LGC_KNN_MAX_BAND: items (accumulator and votes) of one workgroup
 RERANK_MAX_CAND = 256  # LGC_RERANK_MAX_CAND
 HARDNEG_MAX_CAND = 256 # LGC_HARDNEG_MAX_CAND
 RANK_SEEN_MODES = {"zero": 0, "remove": 1}   # LGC_RANK_SEEN_ZERO, LGC_RANK_SEEN_REMOVE

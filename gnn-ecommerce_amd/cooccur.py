@@ -10,7 +10,8 @@ has one right answer, bit for bit; the order is ``mask_topk``'s, equal scores by
 
 CPU tensors take a torch restatement (a dense integer count panel for the asked rows, the three formulas in float32, a
 stable sort by the total order's keys): the definition the host tests hold to the numpy reference, not a serving path.
-What this does NOT do: basket queries (a sum over several items), weighted events, k above 64, several devices.
+What this does NOT do: weighted events, k above 64, several devices.  Basket queries (a sum of similarities over several
+items, the item-kNN recommender) are ``itemknn.py``, which takes this module's result as its neighbour table.
 """
 from __future__ import annotations
 

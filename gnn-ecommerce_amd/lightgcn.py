@@ -16,7 +16,8 @@ own items (``explain``); ``similar_items`` answers "which items are like this on
 ``rerank_diverse`` and ``list_diversity`` re-rank a candidate list by greedy maximal marginal relevance and measure the
 intra-list diversity of the result (``rerank``); ``recommend_filtered``, ``item_audience`` and ``similar_users`` retrieve across
 two tables with a catalogue filter and per-request exclusion lists that REMOVE what they list (``retrieve``); ``bought_together`` answers "customers who bought this also bought" from the
-purchase lists alone, without the embedding (``cooccur``).  What changes is underneath: propagation is the HIP CSR-SpMM with
+purchase lists alone, without the embedding (``cooccur``), and ``recommend_itemknn`` ranks items for users and sessions from
+those neighbour lists, the item-kNN baseline (``itemknn``).  What changes is underneath: propagation is the HIP CSR-SpMM with
 the layer sum fused (``propagate.propagate_sum``) and pair scoring is one gather-dot kernel.
 """
 from __future__ import annotations
@@ -38,6 +39,7 @@ from .paths import shortest_paths
 from .similar import METRICS, item_neighbors, row_rnorm
 from .retrieve import BuyerLists, request_lists, retrieve_topk
 from .cooccur import MEASURES, CoPurchase
+from .itemknn import ItemKNN
 from .fullrank import evaluate_full_rank
 from .propagate import (DEFAULT_WORKSPACE_BYTES, TOPK_MAX, PositiveLists, RegHook, SeenLists, bpr_loss_fused, column_sums,
                         evaluate_ranking, evaluate_topk, mask_topk, pair_dot, propagate_sum, recommend_topk,
@@ -556,6 +558,49 @@ class LightGCN(torch.nn.Module):
             _native.require_device(edge_index, "edge_index")
             lists = CoPurchase.from_edges(edge_index, n_users, n_items)
         return lists.neighbors(ids, k, measure, min_count, item_ok)
+
+    # -- the item-kNN baseline: recommendations from the neighbour table alone ----------------------
+    def recommend_itemknn(self, edge_index, edge_weight, n_users, n_items, users=None, sessions=None, k: int = 20, knn=None,
+                          kn: int = 64, measure: str = "cosine", seen=None, item_ok=None):
+        """``(index int64 [n, k], value fp32 [n, k], votes int32 [n, k])`` on the device: item-kNN recommendations, per
+        user of ``users`` (their purchase lists are the baskets, the purchased items removed) or per session of
+        ``sessions`` (a ``SessionLists``, its weights applied, its own items removed); exactly one of the two is given.
+        A prebuilt ``itemknn.ItemKNN`` is taken as ``knn``; otherwise one is fitted here with ``kn`` neighbours an item by
+        ``measure``, from ``seen`` (a ``SeenLists``) or, without it, from every edge of ``edge_index`` as
+        ``bought_together`` does.  ``item_ok``: bool or uint8 ``[n_items]``, items that may be returned.  It reads no
+        embedding and triggers no propagation.  See ``itemknn.knn_recommend``."""
+        n_users, n_items = int(n_users), int(n_items)
+        if n_users < 1 or n_items < 1 or n_users + n_items != self.num_nodes:
+            raise ValueError(f"n_users {n_users} + n_items {n_items} != {self.num_nodes} nodes")
+        if (users is None) == (sessions is None):
+            raise ValueError("exactly one of users and sessions must be given")
+        if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= _native.KNN_MAX_K:
+            raise ValueError(f"k must be an integer in [1, {_native.KNN_MAX_K}]")
+        if isinstance(kn, bool) or not isinstance(kn, int) or not 1 <= kn <= _native.KNN_MAX_NEIGHBORS:
+            raise ValueError(f"kn must be an integer in [1, {_native.KNN_MAX_NEIGHBORS}]")
+        if not isinstance(measure, str) or measure not in MEASURES:
+            raise ValueError(f"measure must be one of {list(MEASURES)}, got {measure!r}")
+        item_ok = self._ok_mask(item_ok, n_items, "item_ok")
+        if sessions is not None and not isinstance(sessions, SessionLists):
+            raise TypeError("sessions must be a SessionLists")
+        ids = None if users is None else self._id_tensor(users, "users")
+        if knn is None:
+            if seen is not None:
+                if not isinstance(seen, SeenLists):
+                    raise TypeError("seen must be a SeenLists or None")
+                _native.require_device(seen.ptr, "seen.ptr")
+                lists = CoPurchase.from_seen(seen, n_users, n_items)
+            else:
+                if not (torch.is_tensor(edge_index) and edge_index.dim() == 2):
+                    raise ValueError("seen=None needs edge_index as an int64 [2, E] tensor (CoPurchase.from_edges)")
+                _native.require_device(edge_index, "edge_index")
+                lists = CoPurchase.from_edges(edge_index, n_users, n_items)
+            knn = ItemKNN.fit(lists, kn, measure)
+        elif not isinstance(knn, ItemKNN) or knn.n_items != n_items:
+            raise TypeError(f"knn must be an ItemKNN over {n_items} items or None")
+        if sessions is not None:
+            return knn.recommend_sessions(sessions, k, item_ok=item_ok)
+        return knn.recommend(ids, k, item_ok=item_ok)
 
     # -- k recommendations that are not k variants of one product ---------------------------------
     def _item_table(self, edge_index, edge_weight, n_users, n_items) -> Tensor:

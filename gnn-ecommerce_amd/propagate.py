@@ -1495,8 +1495,18 @@ def evaluate_ranking(users_table: Tensor, items: Tensor, seen: Optional[SeenList
     ``evaluate_topk(k=cutoff)`` returns.  Without users the means are NaN; without ``coverage`` that entry is NaN."""
     cuts = [int(c) for c in cutoffs]
     _host_cutoffs(cuts, TOPK_MAX)
-    n, dev, n_items, n_cut = users.numel(), users.device, items.size(0), len(cuts)
     top = recommend_topk(users_table, users, items, seen, cuts[-1], workspace_bytes)
+    return ranking_result(top, positives, users, cuts, items.size(0), coverage)
+
+
+def ranking_result(top: Tensor, positives: PositiveLists, users: Tensor, cuts, n_items: int, coverage: bool = True,
+                   short_rows: bool = False) -> RankingResult:
+    """The metrics half of ``evaluate_ranking`` for ranked rows from ANY source (``top`` int64 [n, max(cuts)], ``cuts`` a
+    list of ascending ints): lgc_rank_metrics, lgc_column_sums and (``coverage``) lgc_topk_coverage, one host sync.
+    ``short_rows``: rows may end in -1, the empty places of a source with fewer than k candidates; they hit nothing (an
+    entry is only compared), and what lgc_topk_coverage reports about them -- they mark nothing -- is dropped: the status
+    word is put back to what it was before that launch."""
+    n, dev, n_cut = users.numel(), users.device, len(cuts)
     hits, metrics, bits = rank_metrics(top, positives, users, cuts, return_bits=True)
     nan = tuple(float("nan") for _ in cuts)
     if n == 0:
@@ -1507,7 +1517,10 @@ def evaluate_ranking(users_table: Tensor, items: Tensor, seen: Optional[SeenList
     sums = column_sums(torch.cat([metrics.view(n, n_cut * _native.RM_COUNT), hits.to(torch.float64)], dim=1))
     parts = [sums.view(torch.int64), _status(dev)[:1].to(torch.int64)]
     if coverage:
+        before = _status(dev).clone() if short_rows else None
         parts.append(topk_coverage(top, cuts, n_items)[0])
+        if short_rows:
+            _status(dev).copy_(before)
     host = torch.cat(parts).cpu()                                        # the one sync
     width = n_cut * (_native.RM_COUNT + 1)
     if int(host[width]) & _native.ST_INDEX_OOB:

@@ -39,7 +39,12 @@ returns what upstream returns, ``[{'items': [[k item indices], ...]}]``.  What d
     "jaccard" (optional, default "cosine"), "min_count": int (optional, at least 1), "allow": [item ids] | "deny": [item ids]
     (optional)}`` asks what is BOUGHT TOGETHER with items: it is answered with ``{"items": [[...]], "scores": [[...]],
     "counts": [[...]]}``, per item the items that share most buyers with it, their scores and the numbers of shared buyers,
-    from the handler's purchase lists alone (``cooccur.CoPurchase``, built once at ``initialize``); the model is not asked.
+    from the handler's purchase lists alone (``cooccur.CoPurchase``, built once at ``initialize``); the model is not asked;
+  * a body ``{"itemknn": [{"items": [item ids], "weights": [...] (optional)}, ...], "k": int (optional, 1 .. 64, default 20),
+    "allow": [item ids] | "deny": [item ids] (optional)}`` asks the ITEM-KNN baseline about baskets: it is answered with
+    ``{"items": [[...]], "scores": [[...]], "votes": [[...]]}``, per basket the items with the best sum of co-purchase
+    similarities to the basket's items, the basket's own items removed, their scores and how many basket items voted for each
+    (``itemknn.ItemKNN``, fitted once, on first use, from the handler's ``CoPurchase``); the model is not asked.
 """
 from __future__ import annotations
 
@@ -55,6 +60,7 @@ from .lightgcn import LightGCN
 from .propagate import SeenLists
 from .retrieve import BuyerLists
 from .cooccur import MEASURES, CoPurchase
+from .itemknn import ItemKNN
 from .rerank import check_lam
 from .similar import METRICS
 
@@ -355,6 +361,62 @@ class RecommendHandler:
                 "scores": [[row[j] for j in js] for row, js in zip(value, keep)],
                 "counts": [[row[j] for j in js] for row, js in zip(count, keep)]}
 
+    def parse_itemknn(self, body):
+        """``(lists, k, item_ok)`` of a body ``{"itemknn": [{"items": [...], "weights": optional}, ...], "k": optional,
+        "allow" | "deny": optional}``: ``lists`` one ``(items, weights or None)`` pair per basket, ``item_ok`` a host uint8
+        ``[n_items]`` tensor or None.  A malformed body or basket raises ValueError, an id outside the catalogue IndexError."""
+        unknown = set(body) - {"itemknn", "k", "allow", "deny"}
+        if unknown or "itemknn" not in body:
+            raise ValueError(f"request body: expected 'itemknn' and optionally 'k', 'allow' or 'deny'; got {sorted(map(str, body))}")
+        if "allow" in body and "deny" in body:
+            raise ValueError("request body: 'allow' and 'deny' do not combine")
+        baskets, k = body["itemknn"], body.get("k", self.k)
+        if not isinstance(baskets, (list, tuple)):
+            raise ValueError("request body: 'itemknn' must be a list of baskets, dicts with 'items'")
+        if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= _native.KNN_MAX_K:
+            raise ValueError(f"request body: 'k' must be an integer in [1, {_native.KNN_MAX_K}]")
+        lists = []
+        for pos, el in enumerate(baskets):
+            if not isinstance(el, dict) or set(el) - {"items", "weights"} or "items" not in el:
+                raise ValueError(f"basket {pos}: expected a dict with 'items' and optionally 'weights'")
+            items, weights = self._id_list(el["items"], f"basket {pos}: 'items'"), el.get("weights")
+            if weights is not None:
+                if (not isinstance(weights, (list, tuple))
+                        or any(isinstance(w, bool) or not isinstance(w, (int, float)) for w in weights)):
+                    raise ValueError(f"basket {pos}: 'weights' must be a list of numbers")
+                if len(weights) != len(items):
+                    raise ValueError(f"basket {pos}: {len(items)} items but {len(weights)} weights")
+                weights = list(weights)
+            lists.append((items, weights))
+        item_ok = None
+        for name in ("allow", "deny"):
+            if name in body:
+                listed = self._id_list(body[name], f"'{name}'")
+                if any(i < 0 or i >= self.n_items for i in listed):
+                    raise IndexError(f"item index outside [0, {self.n_items})")
+                item_ok = torch.full((self.n_items,), 1 if name == "deny" else 0, dtype=torch.uint8)
+                item_ok[torch.tensor(listed, dtype=torch.int64)] = 0 if name == "deny" else 1
+        if any(i < 0 or i >= self.n_items for items, _ in lists for i in items):
+            raise IndexError(f"item index outside [0, {self.n_items})")
+        return lists, k, item_ok
+
+    def inference_itemknn(self, lists, k: int, item_ok):
+        """Per basket the ``k`` items with the best sum of co-purchase similarities to the basket's items, their scores and
+        votes, best first, the basket's own items removed; empty places dropped.  The neighbour table is fitted on first
+        use from the purchase lists and kept."""
+        if not lists:
+            return {"items": [], "scores": [], "votes": []}
+        if getattr(self, "itemknn", None) is None:
+            if getattr(self, "copurchase", None) is None:
+                self.copurchase = CoPurchase.from_seen(self.seen, self.n_users, self.n_items)
+            self.itemknn = ItemKNN.fit(self.copurchase)
+        index, value, votes = self.itemknn.recommend_sessions(SessionLists.from_lists(lists, self.device), k, item_ok=item_ok)
+        index, value, votes = index.cpu().tolist(), value.cpu().tolist(), votes.cpu().tolist()
+        keep = [[j for j, i in enumerate(row) if i >= 0] for row in index]
+        return {"items": [[row[j] for j in js] for row, js in zip(index, keep)],
+                "scores": [[row[j] for j in js] for row, js in zip(value, keep)],
+                "votes": [[row[j] for j in js] for row, js in zip(votes, keep)]}
+
     def parse_diversify(self, body):
         """``(requests, lam, candidates, metric)`` of a body ``{"requests": [...], "diversify": lam, "candidates": optional,
         "metric": optional}``.  A malformed body raises ValueError, a user id outside ``[0, n_users)`` IndexError."""
@@ -444,6 +506,8 @@ class RecommendHandler:
         if isinstance(data, dict):
             if "bought_together" in data:
                 return self.inference_bought_together(*self.parse_bought_together(data))
+            if "itemknn" in data:
+                return self.inference_itemknn(*self.parse_itemknn(data))
             if "similar" in data:
                 return self.inference_similar(*self.parse_similar(data))
             if "audience" in data:

@@ -1370,6 +1370,69 @@ int lgc_cooccur_topk(const int64_t *buyer_ptr, const int64_t *buyer_users, int64
                      int64_t *out_index, float *out_value, int32_t *out_count,
                      void *workspace, size_t workspace_bytes, int32_t *status, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Item-kNN recommender (an addition to ABI 14: exports only): per BASKET -- a user's purchase list, a cart, a session -- the k
+ * items with the best sum of neighbour similarities over the basket's items, from a [n_items, kn] neighbour table
+ * (lgc_cooccur_topk over the whole catalogue, or lgc_item_neighbors).  Accumulation, removal and selection are one launch
+ * per band of the catalogue; the scores live in LDS.  No embedding is read and there is no float atomic anywhere: the same
+ * inputs give the same bytes on every run.
+ *
+ * lgc_knn_recommend: per query the k best eligible items.
+ *   nbr_index, nbr_value  the neighbour table: int64 [n_items, kn] and fp32 of the same shape, rows nbr_stride >= kn
+ *              elements apart in both arrays; kn in 1 .. LGC_KNN_MAX_NEIGHBORS, the width lgc_cooccur_topk and
+ *              lgc_item_neighbors produce.  An entry -1 is an empty place and is ignored.  Any other index outside
+ *              [0, n_items) is skipped and sets LGC_ST_INDEX_OOB in `status`; it is range-checked before an address is formed
+ *              from it.  Elements at or past kn of a row are never read.  The valid indices of a row are distinct, as the two
+ *              producers build them; a row that repeats an index gives an unspecified score for that candidate but never an
+ *              access out of range
+ *   list_ptr, list_items, list_weight  the baskets, a CSR: int64 [n_lists + 1], read on trust as lgc_mask_topk reads its own,
+ *              and int64 item indices, in any order, repeats allowed; list_weight fp32 per entry or NULL.  A basket entry
+ *              outside [0, n_items) is skipped and sets LGC_ST_INDEX_OOB
+ *   list_rows  int64 [n_queries]: query r uses list list_rows[r]; NULL = query r uses list r, and then n_queries <= n_lists.
+ *              A list number outside [0, n_lists) sets LGC_ST_INDEX_OOB and its row is -1 / -inf / 0
+ *   Score      the score of candidate j starts at acc = +0.0f and votes = 0.  The basket's entries are taken in list order
+ *              t = 0, 1, ..., i = list_items[t]: where row i of the table holds j at place p, term = nbr_value[i, p] without
+ *              weights or fl(list_weight[t] * nbr_value[i, p]) with them, then acc = fl(acc + term) and votes += 1.  The
+ *              product and the add are each rounded on their own (-ffp-contract=off), never fused.  A repeated basket entry
+ *              contributes each time it occurs.  The sum order is the basket's, so every output has one right answer, bit for
+ *              bit; NaN and infinities propagate as the additions give them
+ *   Eligible   item j is a candidate iff votes >= min_votes (min_votes >= 1, LGC_E_RANGE otherwise: an item nobody voted
+ *              for is never returned), item_ok is NULL or item_ok[j] != 0 (uint8 [n_items]), and, with exclude_basket != 0,
+ *              j is no valid entry of the basket: such an item is REMOVED, as in lgc_retrieve_topk (there is no zero mode)
+ *   Order      lgc_mask_topk's total order on (score, ascending j).  It is strict, so the result depends neither on `band` nor
+ *              on the order of arrival.  A NaN score comes back as 0x7FFFFFFF and -0 as +0
+ *   k          1 .. LGC_KNN_MAX_K
+ *   band       as in lgc_cooccur_topk: the items one workgroup holds in LDS, one workgroup per (query, band) and a merge
+ *              launch where there is more than one band.  0 = the library chooses (8192);
+ *              an explicit value is a multiple of 64 in [64, LGC_KNN_MAX_BAND] (LGC_E_RANGE otherwise, as for a band that
+ *              cuts the catalogue into more than 2^20 bands): a band costs 8 bytes per item, the accumulator and the votes.
+ *              A band wider than the catalogue holds the catalogue, rounded up to 64.  It exists so that tests can cross band
+ *              edges on small catalogues; it never changes a result
+ *   out_index  int64 [n_queries, k]; out_value fp32 [n_queries, k] or NULL; out_votes int32 [n_queries, k] or NULL: the
+ *              votes of each returned item.  A row with fewer than k candidates ends in -1 / -inf / 0
+ *   workspace  device memory of at least lgc_knn_workspace_bytes(n_queries, n_items, k, band, stream) bytes, 8-byte aligned:
+ *              n_queries * bands * k places of 12 bytes (the candidate word and its votes) where there is more than one band,
+ *              else 0; may be NULL where that is 0.  The size function returns 0 for sizes the call would refuse and grows
+ *              monotonically in n_queries, n_items, k.  It takes the stream of the call it sizes, runs on the host, enqueues
+ *              nothing and reads nothing through the handle (NULL is fine)
+ * Errors before any launch, no output touched: LGC_E_INVAL (a null required pointer -- nbr_index, nbr_value, list_ptr,
+ * list_items, out_index, status --, a negative n_queries or n_lists, nbr_stride < kn); LGC_E_RANGE (k, kn, band or min_votes
+ * out of range, n_items < 1, n_items, n_lists or n_queries >= 2^31 - 1, list_rows NULL with n_queries > n_lists); LGC_E_ALIGN
+ * (an int64 pointer or the workspace not 8-byte aligned, an fp32 or int32 pointer not dword aligned); LGC_E_WORKSPACE (a
+ * workspace that is too small or missing).  n_queries == 0 validates, launches nothing and returns 0.
+ * ------------------------------------------------------------------------------------- */
+#define LGC_KNN_MAX_K 64
+#define LGC_KNN_MAX_NEIGHBORS 64
+#define LGC_KNN_MAX_BAND 16384
+size_t lgc_knn_workspace_bytes(int64_t n_queries, int64_t n_items, int32_t k, int32_t band, void *stream);
+int lgc_knn_recommend(const int64_t *nbr_index, const float *nbr_value, int64_t nbr_stride, int64_t n_items, int32_t kn,
+                      const int64_t *list_ptr, const int64_t *list_items, const float *list_weight, int64_t n_lists,
+                      const int64_t *list_rows, int64_t n_queries,
+                      const uint8_t *item_ok, int32_t exclude_basket, int32_t min_votes,
+                      int32_t k, int32_t band,
+                      int64_t *out_index, float *out_value, int32_t *out_votes,
+                      void *workspace, size_t workspace_bytes, int32_t *status, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
